@@ -20,9 +20,15 @@ run.grad_max_norm = 0.001 of every Backpack.gin; ONE norm over both modules in s
 HBM.  Steps are captured once in a hipGraph (forward + backward [+ optimiser at N = 1]) and replayed; per-step scalars that
 change (learning rate, Adam bias corrections) live in device memory.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+A PLAIN run measures the PRIMARY line only: set-up, warm-up, the timed steps, the JSON line.  `--full` adds everything else this
+file measures or checks -- the secondary stages, the PyTorch-ROCm and CPU baseline legs, the exact-fp32 companions, the 1080p
+frame, the per-kernel / roofline post-pass and the replayed PSNR record.  `--dump-outputs DIR` writes what the last timed step of
+the primary workload computed (loss, rendered colours, updated parameters) as DIR/<name>.npy; all inputs and draws are seeded, so
+two builds of the library can be compared output for output.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 """
 from __future__ import annotations
 
@@ -58,6 +64,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--primary", choices=["stage3", "stage2", "stage1"], default="stage3")
     ap.add_argument("--rays", type=int, default=0, help="override the primary workload's GLOBAL ray count (stage 3 / 2) or per-GPU count (stage 1)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the primary line: secondary stages, baseline legs, exact-fp32 "
+                    "companions, the 1080p frame, the per-kernel / roofline post-pass, the replayed PSNR record (the --only-primary / --no-* "
+                    "switches below trim a --full run; a plain run has none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the primary workload's last timed "
+                    "step computed as DIR/<name>.npy (float32; at most 64 MB in all, large arrays as a fixed seeded sample)")
     ap.add_argument("--only-primary", action="store_true", help="skip the secondary stages and the baseline legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-torch-baseline", action="store_true")
@@ -69,7 +80,10 @@ def parse():
                     "re-uploads the item's tensors from pinned host memory into the step's device batch")
     ap.add_argument("--gemm", choices=["planes", "split", "fp32"], default="planes",
                     help="split = fp16/bf16 hi-lo split MFMA (3 products, fp32 accumulate); fp32 = exact fp32 MFMA")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:       # a plain run does what the headline figure needs and nothing else
+        args.only_primary = args.no_kernel_events = True
+    return args
 
 
 def basedir():
@@ -139,6 +153,11 @@ class Workload:
         self.finish(i, False)
         return loss
 
+    def outputs(self):
+        """What a caller of the step holds after it, next to the loss: the rendered colours of its forward and the updated flat
+        parameter buffers (in a captured step these tensors are static: after a replay they hold that step's values)."""
+        raise NotImplementedError
+
 
 class Stage1(Workload):
     name, scaling = "stage1", "weak"
@@ -173,9 +192,13 @@ class Stage1(Workload):
         from hosnerf_amd.train import stage1_loss
         self.opt.zero_grad()
         rend, hist = self.model(self.batch, self.frac, True, True, 0.1, 1e6)
+        self.last_rgb = rend[-1]["rgb"].detach()
         loss, _ = stage1_loss(rend[-1]["rgb"], self.batch["target"], hist)
         loss.backward()
         return loss.detach()
+
+    def outputs(self):
+        return {"rgb": self.last_rgb, "params_background": self.model.flat_param}
 
 
 def _human_item(rays, rank, stage):
@@ -297,9 +320,13 @@ class Stage2(Workload):
         self.net.split_decoder_backward = True          # the 253 MB decoder gradient is reduced at the decoder's 3.5 MB output
         out = self.net(static_cycle=True, **self.batch)
         self.cycle_count = out.get("cycle_count")
+        self.last_rgb = out["rgb"].detach()
         loss, _ = stage2_losses(out, self.batch)
         loss.backward()
         return loss.detach()
+
+    def outputs(self):
+        return {"rgb": self.last_rgb, "params_human": self.net.flat_param}
 
     def reduce(self):
         _reduce_human(self.net, self.opt, self.static_vol_grad)
@@ -365,9 +392,13 @@ class Stage3(Workload):
         self.hos.human.split_decoder_backward = True
         out = self.hos.render(self.batch, randomized=True, is_train=True, static_cycle=True)
         self.cycle_count = out.get("cycle_count")
+        self.last_rgb = out["rgb"].detach()
         loss, _ = stage3_losses(out, self.batch)
         loss.backward()
         return loss.detach()
+
+    def outputs(self):
+        return {"rgb": self.last_rgb, "params_background": self.hos.model.flat_param, "params_human": self.hos.human.flat_param}
 
     def reduce(self):
         from hosnerf_amd.train import allreduce_flat_grad
@@ -424,6 +455,7 @@ class Stage3LPIPS(Stage3):
         self.hos.human.split_decoder_backward = True
         out = self.hos.render(self.batch, randomized=True, is_train=True, static_cycle=True)
         self.cycle_count = out.get("cycle_count")
+        self.last_rgb = out["rgb"].detach()
         loss, _ = stage3_losses(out, self.batch, lpips=self.lpips)
         loss.backward()
         return loss.detach()
@@ -479,8 +511,31 @@ class Stage3Fresh(Stage3):
 
 
 # ------------------------------------------------------------------------------------------------ timing
-def run_workload(wl, args, dev, rank, world, dist, want_events):
-    """Warm up, capture, time exactly args.steps steps between barriers; returns (seconds [max over ranks], info dict)."""
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: every tensor as <dirname>/<name>.npy, float32.  All files together stay under DUMP_BUDGET_BYTES: an
+    array over its equal share of the budget is written as a fixed sample of its elements (indices drawn once from a seeded
+    generator, ascending, the same for every run and every build; they are stored next to it as <name>.index.npy, float64).
+    Inputs and draws repeat exactly; the outputs of two runs of ONE build still differ in their last bits, because the steps' slab
+    reductions add with floating-point atomics and 25 optimiser steps carry that on: measured at 20 + 5 steps of stage 3, loss
+    within 1e-6, parameters within 1e-5, colours within 2e-4 on the median ray (a ray whose sample crosses a proposal bin: up to 4e-2)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (16 * len(tensors))        # elements per array: 4 B per value + 8 B per index, and headroom
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(777)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            np.save(os.path.join(dirname, name + ".index.npy"), idx.to(torch.float64).numpy())
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
+def run_workload(wl, args, dev, rank, world, dist, want_events, dump_dir=None):
+    """Warm up, capture, time exactly args.steps steps between barriers; returns (seconds [max over ranks], info dict).  `dump_dir`:
+    after the timed steps, the outputs of the last one are written there (`dump_outputs`)."""
     from hosnerf_amd import ops
 
     def barrier():
@@ -606,6 +661,8 @@ def run_workload(wl, args, dev, rank, world, dist, want_events):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
     info = {"launch": launch, "final_loss": float(loss.detach()), "f_cyc": wl.f_cyc() if f_cyc is None else f_cyc}
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"loss": loss.detach(), **wl.outputs()})
     if getattr(getattr(wl, "hos", None), "two_streams", False):
         info["launch"] += "; background branch and human branch on two streams inside the graph"
     if h2d is not None:
@@ -870,6 +927,10 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
 
+    # every draw of the steps (sample jitter, t_rand) comes from torch's default generators, which start each process from a seed of
+    # their own: seeded here, so that a run repeats its inputs exactly
+    torch.manual_seed(777 + rank)
+
     from hosnerf_amd import ops
     ops.set_gemm_mode({"planes": ops.GEMM_PLANES, "split": ops.GEMM_BF16X3, "fp32": ops.GEMM_FP32}[args.gemm])
 
@@ -885,11 +946,11 @@ def main():
             return Stage3Fresh(dev, rank, world, args.rays if (args.rays and args.primary == "stage3") else GLOBAL_RAYS_S3)
         return (Stage3 if name == "stage3" else Stage2)(dev, rank, world, g)
 
-    def measure(name, events, rays_global=None, describe=None, run_args=None):
+    def measure(name, events, rays_global=None, describe=None, run_args=None, dump_dir=None):
         wl = make(name, rays_global)
         if describe is not None:
             wl.describe = describe
-        dt, info, table = run_workload(wl, run_args or args, dev, rank, world, dist, events)
+        dt, info, table = run_workload(wl, run_args or args, dev, rank, world, dist, events, dump_dir)
         steps = (run_args or args).steps
         rays_total = wl.rays_global * steps
         fkey = "stage3" if name in ("stage3_fresh_items", "stage3_with_lpips") else name
@@ -967,7 +1028,7 @@ def main():
                                                        if one_gpu else " (= RCCL on ROCm)"),
                      "rccl_ranks_seen": int(ones.item()), "devices": names}
 
-    prim, table = measure(args.primary, events)
+    prim, table = measure(args.primary, events, dump_dir=args.dump_outputs)
     if rank == 0:
         out.update({
             "metric": f"train rays/sec ({args.primary}: forward + losses + backward + gradient all-reduce + Adam"
@@ -995,19 +1056,20 @@ def main():
         })
         # BASELINE's metric also names "PSNR vs. reference": the held-out PSNR of the HIP path and of the reference's op graph trained side
         # by side (tests/test_gpu_convergence.py) -- REPLAYED from the committed record of that test, not measured by this run
-        try:
-            with open(os.path.join(ROOT, "profiles", "r06_parity_counts.json")) as f:
-                pc = json.load(f)
-            eq = {k.split(".")[1]: {"psnr_db_hip": pc[k]["psnr_hip"], "psnr_db_reference_graph": pc[k]["psnr_oracle"], "steps": pc[k]["steps"]}
-                  for k in ("convergence.stage1", "convergence.stage2", "convergence.stage3") if k in pc}
-            wf = pc.get("trained.stage3.whole_frame_eval[held-out frame, jointly trained weights]")
-            if wf:
-                eq["stage3_whole_frame_eval_same_weights"] = {"psnr_db_hip": wf["psnr_hip"], "psnr_db_reference_graph": wf["psnr_oracle"], "rgb_linf": wf["rgb_linf"]}
-            if eq:
-                out["psnr_vs_reference"] = dict(eq, source="profiles/r06_parity_counts.json (tests/test_gpu_convergence.py on a synthetic scene directory; "
-                                                             "replayed, not measured in this run; the Backpack sequence does not exist offline)")
-        except Exception:
-            pass
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, "profiles", "r06_parity_counts.json")) as f:
+                    pc = json.load(f)
+                eq = {k.split(".")[1]: {"psnr_db_hip": pc[k]["psnr_hip"], "psnr_db_reference_graph": pc[k]["psnr_oracle"], "steps": pc[k]["steps"]}
+                      for k in ("convergence.stage1", "convergence.stage2", "convergence.stage3") if k in pc}
+                wf = pc.get("trained.stage3.whole_frame_eval[held-out frame, jointly trained weights]")
+                if wf:
+                    eq["stage3_whole_frame_eval_same_weights"] = {"psnr_db_hip": wf["psnr_hip"], "psnr_db_reference_graph": wf["psnr_oracle"], "rgb_linf": wf["rgb_linf"]}
+                if eq:
+                    out["psnr_vs_reference"] = dict(eq, source="profiles/r06_parity_counts.json (tests/test_gpu_convergence.py on a synthetic scene directory; "
+                                                                 "replayed, not measured in this run; the Backpack sequence does not exist offline)")
+            except Exception:
+                pass
         if model_shard() > 1:
             out["metric"] += f" -- ONE-GPU TIMING MODEL of rank 0 of {model_shard()} with the sharded volume decoder, collectives replaced by identities"
             out["model_shard"] = model_shard()

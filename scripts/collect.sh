@@ -7,7 +7,7 @@ RND=${1:-r06}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R; O=${2:-gpurun_out/${RND}final}; mkdir -p $O
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu.ids | tail -8 | tee $O/smoke.txt
-timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench_${RND}_final.json 2> $O/bench.err
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/bench_${RND}_final.json 2> $O/bench.err
 for r in 512 1024 2048 4096; do
   timeout 600 python bench.py --primary stage3 --only-primary --rays $r --steps 20 --warmup 3 --no-kernel-events 2>/dev/null | tail -1
 done > $O/${RND}_strong_scaling_sweep.jsonl

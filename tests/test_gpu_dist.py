@@ -95,14 +95,14 @@ def test_bench_two_ranks_share_one_gpu_strong_scaling(shard):
 
 
 def test_bench_default_command_two_ranks_rehearsal():
-    """The command the driver runs at N > 1 -- `bench.py --gpus N --steps K --warmup W`, nothing skipped -- rehearsed as two processes
+    """The command the driver runs at N > 1 -- `bench.py --gpus N --steps K --warmup W --full`, nothing skipped -- rehearsed as two processes
     on the one GPU (gloo stands in for RCCL): the ONE JSON line must carry the proof of who took part (`comm`), the strong-scaling
     primary, the weak-scaling stage-3 leg (4096 rays PER rank, the reference's DDP semantic, 3rd_Complete_HOSNeRF/run.py:173-190),
     the sharded-decoder leg, stage 1 and the 1080p frame -- every secondary leg inside its guard."""
     e = _env()
     e["HOS_BENCH_ONE_GPU"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29543", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"]
+           "--master-port", "29543", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -34,12 +34,10 @@ def test_gin_lite_parses_reference_style_files_and_bindings():
 
 
 def test_reference_gin_files_parse_unchanged():
-    """The reference's own .gin files, when the mount is present (build container)."""
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference mount absent")
-    for rel in ("1st_State-Conditional_Scene/configs/state_mipnerf360/Backpack.gin", "3rd_Complete_HOSNeRF/configs/HOSNeRF/Backpack.gin"):
-        g = gin_lite.parse_file(os.path.join(ref, rel))
+    """The reference's own .gin files (1st_State-Conditional_Scene/configs/state_mipnerf360/Backpack.gin and
+    3rd_Complete_HOSNeRF/configs/HOSNeRF/Backpack.gin, stored byte for byte under tests/golden/gin/)."""
+    for name in ("state_mipnerf360_Backpack.gin", "hosnerf_Backpack.gin"):
+        g = gin_lite.parse_file(os.path.join(ROOT, "tests", "golden", "gin", name))
         assert g["run.model_name"] in ("state_mipnerf360", "hosnerf") and g["run.grad_max_norm"] == 0.001
 
 
