@@ -105,6 +105,7 @@ PROTOTYPES = {
     "hos_raw2outputs_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P],
     "hos_raw2outputs_bwd": [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _F, _I, _I, _P, _I, _P, _I, _P, _P],
     "hos_merge_composite_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
+    "hos_merge_composite_maps_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hos_merge_composite_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P],
     "hos_mlp_chain_weight_bytes": [],
     "hos_mlp_chain_aux_floats": [],

@@ -4,12 +4,15 @@
 //   hos_merge_composite_{fwd,bwd} M:1524-1596: re-project the human samples onto the background ray (C1),
 //                                 fg/bg split + z-sort of 32 background + 128 human samples (C2),
 //                                 masked alpha composite of the merged 160 samples (C3)
+//   hos_merge_composite_maps_fwd  the same forward launch + acc_map / depth_map (M:93-94) and the human / background layer sums
+//                                 (a second instantiation of the same kernel; the rgb-only one is compiled without any of it)
 //
 // The reference does this with torch.sort + three advanced-indexing gathers + cumprod on [B,160,*]
 // temporaries.  Here a ray's 160 keys live in LDS, the (stable) sort is a rank-by-counting pass
 // (160^2/64 compares per lane), and the transmittance is a wave-level product scan.
 // HBM-bound: algorithmic bytes/ray = 4*(33 + 32*4 + 128*(4+3+1) + 6) in, 12 B out (+ 4*160 for total_order).
 #include "hos_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -159,7 +162,20 @@ struct MergeArgs {
     const float* g_rgb; const float* g_hw; float* g_bkg_rgb; float* g_bkg_density; float* g_human; float* g_mask;
 };
 
-__global__ __launch_bounds__(256) void merge_composite_kernel(const MergeArgs a) {
+// per-ray maps of the forward (every pointer may be NULL): acc = sum w, depth = sum w z (M:93-94, un-normalised), and the
+// premultiplied layers of the merged ray split by sample origin (src >= Sb: human) under the SHARED transmittance
+struct MapsOut {
+    float* acc; float* depth;                  // [B]
+    float* rgb_human; float* acc_human;        // [B,3], [B]
+    float* rgb_bkg; float* acc_bkg;            // [B,3], [B]
+};
+
+struct MergeMapsArgs : MergeArgs { MapsOut maps; };
+
+// Args = MergeArgs: the rgb-only forward and the backward (no trace of the maps in its code); Args = MergeMapsArgs: forward + maps
+template <class Args>
+__global__ __launch_bounds__(256) void merge_composite_kernel(const Args a) {
+    constexpr bool MAPS = std::is_same<Args, MergeMapsArgs>::value;
     __shared__ MergeLds lds[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ray_raw = blockIdx.x * 4 + wave;
@@ -244,6 +260,32 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const MergeArgs a)
         if (live && lane == 0) {
             a.rgb[ray * 3] = r; a.rgb[ray * 3 + 1] = g; a.rgb[ray * 3 + 2] = b;
             if (a.idx_fg) a.idx_fg[ray] = fg ? 1 : 0;
+        }
+        if constexpr (MAPS) {
+            const MapsOut* mo = &a.maps;
+            // accumulators of their own, same per-lane order and the same wave_sum tree as r/g/b above: rgb stays bit-identical
+            // to the rgb-only kernel, and human + background differ from the total only by the rounding of the two partial sums
+            float ac = 0.f, dep = 0.f, hs[4] = {0.f, 0.f, 0.f, 0.f}, bs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < CHM; ++k) {
+                if (src[k] < 0) continue;
+                const float w = c.w[k];
+                ac += w;
+                dep += w * L.zs[lane * per + k];
+                if (src[k] >= Sb) { hs[0] += w * col[k][0]; hs[1] += w * col[k][1]; hs[2] += w * col[k][2]; hs[3] += w; }
+                else              { bs[0] += w * col[k][0]; bs[1] += w * col[k][1]; bs[2] += w * col[k][2]; bs[3] += w; }
+            }
+            ac = wave_sum(ac); dep = wave_sum(dep);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { hs[q] = wave_sum(hs[q]); bs[q] = wave_sum(bs[q]); }
+            if (live && lane == 0) {
+                if (mo->acc) mo->acc[ray] = ac;
+                if (mo->depth) mo->depth[ray] = dep;
+                if (mo->rgb_human) { mo->rgb_human[ray * 3] = hs[0]; mo->rgb_human[ray * 3 + 1] = hs[1]; mo->rgb_human[ray * 3 + 2] = hs[2]; }
+                if (mo->acc_human) mo->acc_human[ray] = hs[3];
+                if (mo->rgb_bkg) { mo->rgb_bkg[ray * 3] = bs[0]; mo->rgb_bkg[ray * 3 + 1] = bs[1]; mo->rgb_bkg[ray * 3 + 2] = bs[2]; }
+                if (mo->acc_bkg) mo->acc_bkg[ray] = bs[3];
+            }
         }
         if (live && a.total_order)
             for (int j = lane; j < St; j += 64) a.total_order[(size_t)ray * St + j] = (fg && j < S) ? L.order[j] : -1;
@@ -330,11 +372,18 @@ extern "C" int hos_raw2outputs_bwd(const float* g_rgb, const float* g_weights, c
     return hos_launch_status();
 }
 
-static int merge_launch(MergeArgs& a, hipStream_t s) {
+static int merge_launch(MergeArgs& a, hipStream_t s, const MapsOut* mo = nullptr) {
     if (!a.bkg_tdist || !a.bkg_rgb || !a.bkg_density || !a.human || !a.pts || !a.mask || !a.rays_o || !a.rays_d || !a.A)
         return HOS_E_ARG;
     if (a.B <= 0 || a.Sb <= 0 || a.Sh <= 0 || a.Sb + a.Sh > MAXS) return HOS_E_SHAPE;
-    hipLaunchKernelGGL(merge_composite_kernel, dim3(hos_cdiv(a.B, 4)), dim3(256), 0, s, a);
+    if (mo) {
+        MergeMapsArgs am{};
+        static_cast<MergeArgs&>(am) = a;
+        am.maps = *mo;
+        hipLaunchKernelGGL(merge_composite_kernel<MergeMapsArgs>, dim3(hos_cdiv(a.B, 4)), dim3(256), 0, s, am);
+    } else {
+        hipLaunchKernelGGL(merge_composite_kernel<MergeArgs>, dim3(hos_cdiv(a.B, 4)), dim3(256), 0, s, a);
+    }
     return hos_launch_status();
 }
 
@@ -351,6 +400,23 @@ extern "C" int hos_merge_composite_fwd(const float* bkg_tdist, const float* bkg_
     a.rgb = rgb; a.idx_fg = idx_fg; a.total_order = total_order; a.hw_sorted = human_weights_sorted; a.z_h = z_human;
     if (!rgb) return HOS_E_ARG;
     return merge_launch(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hos_merge_composite_maps_fwd(const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
+                                            const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,
+                                            const float* rays_o_bkg, const float* rays_d_bkg, const float* smpl_to_world,
+                                            const int32_t* tiny_d_flag, int B, int Sb, int Sh, float thre_fg,
+                                            float* rgb, int32_t* idx_fg, int32_t* total_order,
+                                            float* acc, float* depth, float* rgb_human, float* acc_human,
+                                            float* rgb_bkg, float* acc_bkg, hos_stream_t stream) {
+    MergeArgs a{};
+    a.bkg_tdist = bkg_tdist; a.bkg_rgb = bkg_rgb; a.bkg_density = bkg_density; a.human = human_rgbsigma;
+    a.pts = newsmpl_pts; a.mask = pts_mask; a.rays_o = rays_o_bkg; a.rays_d = rays_d_bkg; a.A = smpl_to_world;
+    a.tiny_d_flag = tiny_d_flag; a.B = B; a.Sb = Sb; a.Sh = Sh; a.thre_fg = thre_fg;
+    a.rgb = rgb; a.idx_fg = idx_fg; a.total_order = total_order;
+    if (!rgb) return HOS_E_ARG;
+    const MapsOut mo{acc, depth, rgb_human, acc_human, rgb_bkg, acc_bkg};
+    return merge_launch(a, static_cast<hipStream_t>(stream), &mo);
 }
 
 extern "C" int hos_merge_composite_bwd(const float* g_rgb, const float* g_human_weights_sorted,

@@ -76,11 +76,43 @@ def _local(tensors: Dict[str, torch.Tensor], n: int, group) -> Dict[str, torch.T
     return {k: v.index_select(1 if k == "rays" else 0, idx) for k, v in tensors.items()}
 
 
+# column layout of a ray list's packed maps (one [n, C] tensor per list, so that a frame still costs one gather per list)
+FG_MAP_COLS = {"rgb": slice(0, 3), "alpha": 3, "depth": 4, "rgb_human": slice(5, 8), "alpha_human": 8}      # [n_fg, 9]
+BG_MAP_COLS = {"rgb": slice(0, 3), "alpha": 3, "depth": 4}                                                  # [n_bg, 5]
+FG_MAP_WIDTH, BG_MAP_WIDTH = 9, 5
+
+
+def pack_maps(out: Dict[str, torch.Tensor], cols: Dict) -> torch.Tensor:
+    """The maps of one rendered chunk (`HOSNeRF.render(maps=True)` / `render_bkg_only(maps=True)`) as one [n, C] tensor."""
+    return torch.cat([out[k] if out[k].dim() == 2 else out[k][:, None] for k in cols], 1)
+
+
+def assemble_maps(H: int, W: int, bgcolor, ray_mask: torch.Tensor, ray_mask_bkg: torch.Tensor, fg_packed: torch.Tensor,
+                  bg_packed: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """Scatter the two ray lists' packed maps into whole-frame buffers the way `rendered` is assembled (M:1456-1459):
+    `rgb` [H*W,3] starts from bgcolor / 255 (M:1311-1313), `alpha` / `depth` [H*W] and the human layer `rgb_human` [H*W,3] /
+    `alpha_human` [H*W] from zero; rays through the human box (`ray_mask`) take all five from `fg_packed` [n_fg,9], rays that
+    miss it (`ray_mask_bkg`) take rgb / alpha / depth from `bg_packed` [n_bg,5] and have no human layer."""
+    dev = fg_packed.device
+    bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev).reshape(3) / 255.0
+    maps = {"rgb": bg.expand(H * W, 3).clone(), "alpha": torch.zeros(H * W, device=dev), "depth": torch.zeros(H * W, device=dev),
+            "rgb_human": torch.zeros(H * W, 3, device=dev), "alpha_human": torch.zeros(H * W, device=dev)}
+    for k, c in FG_MAP_COLS.items():
+        maps[k][ray_mask] = fg_packed[:, c]
+    for k, c in BG_MAP_COLS.items():
+        maps[k][ray_mask_bkg] = bg_packed[:, c]
+    return maps
+
+
 def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = False, group=None,
-                 cache_prologue: bool = True) -> torch.Tensor:
+                 cache_prologue: bool = True, maps: bool = False):
     """One frame of `free_view` / `test_metrics` / `progress` (M:1320-1458).  `frame` carries the keys of the reference's
     evaluation batch (freeview.py:284-335).  Returns `rendered` [H*W, 3] on the device (every rank holds the whole frame
-    when `group` is given).  `randomized` is False in free_view/test_metrics and True in progress (M:720-723)."""
+    when `group` is given).  `randomized` is False in free_view/test_metrics and True in progress (M:720-723).
+
+    `maps=True` returns a dict of whole-frame device buffers instead: `rgb` [H*W,3] (the same `rendered`), `alpha` [H*W],
+    `depth` [H*W] (`alpha_onlyfg, depth_onlyfg` / `bkg_alpha, bkg_depth` of the reference's frame loops, M:809-835) and the
+    human-object layer `rgb_human` [H*W,3] (premultiplied) / `alpha_human` [H*W]; see `assemble_maps`."""
     H, W = int(frame["img_height"]), int(frame["img_width"])
     dev = frame["rays_o_bkg"].device
     per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
@@ -95,8 +127,11 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
             sl = slice(i, i + chunk_bkg)
             b = dict(per_frame)
             b.update({k: (v[:, sl] if k == "rays" else v[sl]).contiguous() for k, v in fg.items()})
-            parts.append(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False)["rgb"])
-        rgb = torch.cat(parts, 0) if parts else torch.zeros(0, 3, device=dev)
+            if maps:
+                parts.append(pack_maps(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False, maps=True), FG_MAP_COLS))
+            else:
+                parts.append(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False)["rgb"])
+        rgb = torch.cat(parts, 0) if parts else torch.zeros(0, FG_MAP_WIDTH if maps else 3, device=dev)
         # ---- rays that miss it: background only (M:1434-1452)
         n_bg = frame["rays_o_bkg_only"].shape[0]
         bg_rays = _local({"rays_o": frame["rays_o_bkg_only"], "rays_d": frame["rays_d_bkg_only"],
@@ -105,11 +140,16 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
         for i in range(0, bg_rays["radii"].shape[0], chunk_bkg):
             bb = {k: v[i:i + chunk_bkg].contiguous() for k, v in bg_rays.items()}
             bb["times"] = frame["time"]
-            parts.append(hos.render_bkg_only(bb, randomized=randomized, is_train=False))
-        bkg_rgbs = torch.cat(parts, 0) if parts else torch.zeros(0, 3, device=dev)
+            if maps:
+                parts.append(pack_maps(hos.render_bkg_only(bb, randomized=randomized, is_train=False, maps=True), BG_MAP_COLS))
+            else:
+                parts.append(hos.render_bkg_only(bb, randomized=randomized, is_train=False))
+        bkg_rgbs = torch.cat(parts, 0) if parts else torch.zeros(0, BG_MAP_WIDTH if maps else 3, device=dev)
         if group is not None:
             rgb = gather_frame(rgb, n_fg, group) if n_fg else rgb
             bkg_rgbs = gather_frame(bkg_rgbs, n_bg, group) if n_bg else bkg_rgbs
+    if maps:
+        return assemble_maps(H, W, frame.get("bgcolor", (0.0, 0.0, 0.0)), frame["ray_mask"], frame["ray_mask_bkg"], rgb, bkg_rgbs)
     bg = torch.as_tensor(frame.get("bgcolor", (0.0, 0.0, 0.0)), dtype=torch.float32, device=dev).reshape(3) / 255.0
     rendered = bg.expand(H * W, 3).clone()                                        # M:1311-1313
     rendered[frame["ray_mask"]] = rgb                                             # M:1456-1459

@@ -111,3 +111,35 @@ def save_image(path: str, rendered: torch.Tensor, H: int, W: int):
     from .eval import to_8b_image
     os.makedirs(os.path.dirname(path), exist_ok=True)
     Image.fromarray(to_8b_image(rendered.view(H, W, 3)).cpu().numpy()).save(path)
+
+
+def depth_preview(depth: np.ndarray) -> np.ndarray:
+    """8-bit preview of a depth map, normalised by the frame's own 2nd..98th percentile (near = dark).  The expected depth of
+    the background reaches the far plane (1e6), so a min/max normalisation would show nothing of the subject."""
+    d = np.asarray(depth, dtype=np.float64)
+    lo, hi = np.percentile(d, 2.0), np.percentile(d, 98.0)
+    return (np.clip((d - lo) / max(hi - lo, 1e-12), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def save_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W: int) -> Dict[str, str]:
+    """Write the maps of one frame (`eval.render_frame(maps=True)`) next to its colour image; returns {kind: path}:
+      <name>_depth.npy        float32 [H,W], the un-normalised expected depth `depth_map` (M:94)
+      <name>_depth.png        its 8-bit preview (`depth_preview`)
+      <name>_alpha.png        opacity `acc_map` (M:93), 8-bit greyscale
+      <name>_alpha_human.png  opacity of the human-object layer, 8-bit greyscale
+      <name>_human.png        the human-object layer as RGBA: colour un-premultiplied where alpha_human > 0, alpha = alpha_human"""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    to8 = lambda x: (np.clip(x, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    host = {k: maps[k].detach().float().cpu().numpy() for k in ("depth", "alpha", "alpha_human", "rgb_human")}
+    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in ("depth.npy", "depth.png", "alpha.png", "alpha_human.png", "human.png")}
+    depth = host["depth"].reshape(H, W).astype(np.float32)
+    np.save(paths["depth.npy"], depth)
+    Image.fromarray(depth_preview(depth)).save(paths["depth.png"])
+    Image.fromarray(to8(host["alpha"].reshape(H, W))).save(paths["alpha.png"])
+    ah = host["alpha_human"].reshape(H, W)
+    Image.fromarray(to8(ah)).save(paths["alpha_human.png"])
+    colour = host["rgb_human"].reshape(H, W, 3)
+    straight = np.where(ah[..., None] > 0.0, colour / np.where(ah > 0.0, ah, 1.0)[..., None], 0.0)
+    Image.fromarray(np.concatenate([to8(straight), to8(ah)[..., None]], -1), mode="RGBA").save(paths["human.png"])
+    return paths

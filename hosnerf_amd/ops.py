@@ -1329,6 +1329,38 @@ def merge_composite(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts
                                  rays_o_bkg.contiguous(), rd, newsmpl_to_scale_world.contiguous().float(), tiny, thre_fg)
 
 
+MAP_KEYS = ("acc", "depth", "rgb_human", "acc_human", "rgb_bkg", "acc_bkg")
+
+
+def merge_composite_maps(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts, pts_mask, rays_o_bkg, rays_d_bkg,
+                         newsmpl_to_scale_world, thre_fg: float = 5e-3, want=MAP_KEYS):
+    """The forward of `merge_composite` with the maps of the reference's composite, ONE launch (hos_merge_composite_maps_fwd):
+    a dict with `rgb` [B,3], `idx_fg` [B] int32, `total_order` [B,Sb+Sh] int32 (bit-identical to `merge_composite`) and, for
+    every name in `want`, `acc` / `depth` [B] (acc_map / depth_map of M:93-94, depth not divided by acc), `rgb_human` [B,3] /
+    `acc_human` [B] and `rgb_bkg` / `acc_bkg` (premultiplied layers under the merged ray's shared transmittance).
+    Forward only: inputs are detached and nothing returned here is part of an autograd graph."""
+    unknown = [k for k in want if k not in MAP_KEYS]
+    if unknown:
+        raise ValueError(f"merge_composite_maps: unknown map(s) {unknown}; choose from {MAP_KEYS}")
+    det = lambda t: t.detach().contiguous()
+    rd = det(rays_d_bkg)
+    dev = rd.device
+    B, Sb = bkg_density.shape
+    Sh = pts_mask.shape[1]
+    tiny = torch.empty(1, dtype=torch.int32, device=dev)
+    call("hos_any_abs_below", ptr(rd), rd.numel(), 1e-5, ptr(tiny, torch.int32))
+    out = {"rgb": torch.empty(B, 3, device=dev), "idx_fg": torch.empty(B, dtype=torch.int32, device=dev),
+           "total_order": torch.empty(B, Sb + Sh, dtype=torch.int32, device=dev)}
+    for k in want:
+        out[k] = torch.empty((B, 3) if k.startswith("rgb") else (B,), device=dev)
+    tens = [det(t) for t in (bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts, pts_mask, rays_o_bkg)]
+    A = det(newsmpl_to_scale_world).float()
+    call("hos_merge_composite_maps_fwd", *[ptr(t) for t in tens], ptr(rd), ptr(A), ptr(tiny, torch.int32), B, Sb, Sh,
+         float(thre_fg), ptr(out["rgb"]), ptr(out["idx_fg"], torch.int32), ptr(out["total_order"], torch.int32),
+         *[ptr(out.get(k)) for k in MAP_KEYS])
+    return out
+
+
 # ------------------------------------------------------------------------------------------ per-frame prologue (P2, P3)
 POSE_PARAM_ORDER = ("block_mlps.0", "block_mlps.2", "block_mlps.4", "block_mlps_dstR.0", "block_mlps_dstR.2", "block_mlps_dstT.0",
                     "block_mlps_dstT.2")          # (weight, bias) pairs in this order = the 14 pointers of hos_pose_refine_*

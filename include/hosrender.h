@@ -469,6 +469,22 @@ int hos_merge_composite_fwd(const float* bkg_tdist, const float* bkg_rgb, const 
                             const int32_t* tiny_d_flag, int B, int Sb, int Sh, float thre_fg,
                             float* rgb, int32_t* idx_fg, int32_t* total_order, float* human_weights_sorted,
                             float* z_human, hos_stream_t stream);
+/* The same forward launch with the per-ray maps the reference's composite returns next to rgb_map and its frame loops keep
+ * (`acc_map`, `depth_map` of `_raw2outputs`, M:93-94, as called at M:1586 on fg rays and M:1592 on bg rays; `alpha_onlyfg,
+ * depth_onlyfg` / `bkg_alpha, bkg_depth` of M:809-835; `net_output['alpha'|'depth']`, M:1615), plus the layer split:
+ *   acc = sum_j w_j,  depth = sum_j w_j z_j  (z_j: the merged sorted depth on fg rays, bkg tdist[:-1] on bg rays; NOT divided by acc)
+ *   rgb_human / acc_human = sum over the human samples (total_order >= Sb) of w_j c_j / w_j, rgb_bkg / acc_bkg over the others:
+ *   premultiplied layers under the SHARED transmittance of the merged ray, so human + bkg == total up to fp32 rounding; the
+ *   human layer of a bg ray (idx_fg == 0) is exactly 0.
+ * rgb / idx_fg / total_order are bit-identical to hos_merge_composite_fwd.  Forward only (no gradient flows through the maps);
+ * idx_fg, total_order and each of the six map pointers may be NULL. */
+int hos_merge_composite_maps_fwd(const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
+                                 const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,
+                                 const float* rays_o_bkg, const float* rays_d_bkg, const float* smpl_to_world,
+                                 const int32_t* tiny_d_flag, int B, int Sb, int Sh, float thre_fg,
+                                 float* rgb, int32_t* idx_fg, int32_t* total_order,
+                                 float* acc, float* depth, float* rgb_human, float* acc_human,
+                                 float* rgb_bkg, float* acc_bkg, hos_stream_t stream);
 int hos_merge_composite_bwd(const float* g_rgb, const float* g_human_weights_sorted,
                             const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
                             const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,

@@ -310,7 +310,8 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     `freeview.frame_idx` (images under <logdir>/freeview_vis_newtrans/view_<idx>), every frame through `eval.render_frame`; with
     several ranks each frame's rays are split over the group.  Writes <logdir>/results.json."""
     from hosnerf_amd import eval as ev, select_option
-    from hosnerf_amd.freeview import save_image
+    from hosnerf_amd.freeview import save_image, save_maps
+    render_maps = bool(kw.get("render_maps", False))          # run.render_maps: depth / opacity / human-layer files next to each frame
     if model_name != "hosnerf":
         raise SystemExit("run.run_eval / run.run_render: full-frame rendering is the stage-3 (`hosnerf`) launcher's; stages 1 / 2 report their training loss only")
     if scene is None:
@@ -332,10 +333,13 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         psnrs = {}
         for i in idxs:
             fr = scene.eval_frame(i, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group)
+            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps)
+            frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
             psnrs[fr["frame_name"]] = ev.psnr_metric(rendered, ev.truth_frame(fr))
             if rank == 0:
                 save_image(os.path.join(logdir, "test_vis", fr["frame_name"] + ".png"), rendered, int(fr["img_height"]), int(fr["img_width"]))
+                if render_maps:
+                    save_maps(os.path.join(logdir, "test_vis"), fr["frame_name"], frame_maps, int(fr["img_height"]), int(fr["img_width"]))
         out["test"] = {"psnr": float(sum(psnrs.values()) / len(psnrs)), "frames": psnrs}
         if rank == 0:
             print(f"[run] Test PSNR is {out['test']['psnr']:.4f} over {len(psnrs)} frames")
@@ -346,11 +350,15 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         psnrs = []
         for k in range(count):
             fr = scene.freeview_frame(fidx, k, total, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group)
+            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps)
+            frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
             psnrs.append(ev.psnr_metric(rendered, ev.truth_frame(fr)))          # the reference reports it against the training frame too (M:1462)
             if rank == 0:
                 save_image(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}", f"image-{k:05d}.jpg"), rendered,
                            int(fr["img_height"]), int(fr["img_width"]))
+                if render_maps:
+                    save_maps(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}", frame_maps,
+                              int(fr["img_height"]), int(fr["img_width"]))
         out["freeview"] = {"frame_idx": fidx, "frames": count, "of": total, "psnr_vs_training_frame": float(sum(psnrs) / len(psnrs))}
         if rank == 0:
             print(f"[run] Freeview: {count} of {total} cameras about frame {fidx} written to {os.path.join(logdir, 'freeview_vis_newtrans')}")
