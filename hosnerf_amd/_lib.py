@@ -62,6 +62,8 @@ PROTOTYPES = {
     "hos_unpack_patches_bwd": [_P, _P, _L, _F, _F, _F, _P, _P],
     "hos_camera_rays": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     "hos_rays_aabb": [_P, _P, _L, _P, _P, _P, _P, _P],
+    "hos_frame_rays_compact": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "hos_frame_paint": [_P, _P, _I, _P, _I, _I, _P, _P, _P],
     "hos_deconv3d_col2im": [_P, _P, _I, _I, _F, _I, _P, _P],
     "hos_deconv3d_im2col": [_P, _I, _I, _P, _P],
     "hos_bias_lrelu": [_P, _P, _L, _I, _F, _I, _P],

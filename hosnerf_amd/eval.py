@@ -157,6 +157,40 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
     return rendered
 
 
+def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = False):
+    """One frame of `test_tpose` (M:614-629): the human-object network alone over every ray of the frame's box, `_raw2outputs`
+    over the frame's background colour, no scene.  `frame` is a `tpose.tpose_frame` batch (the reference's T-pose batch plus the
+    `slot` / `count` of `rays.frame_rays_compact`, `time` and `iter_val`).  Under `evaluating(hos)`:
+      1. one `frame_prologue`;
+      2. the human network over all `count` rays with `with_cycle=False` (it chunks by `cfg.chunk` itself);
+      3. `ops.raw2outputs(human_rgbsigma, z_vals, rays_d, pts_mask, bgcolor)` (M:621-623);
+      4. `rays.paint_frame` (M:610-612, :627, :629).
+    Returns the float frame [H*W,3]; `maps=True` returns a dict `rgb` / `alpha` [H*W] / `depth` [H*W] (`alpha_`, `depth_` of the same
+    `_raw2outputs` call, painted over 0).  `want_u8=True` adds the paint kernel's 8-bit frame: a (frame-or-dict, uint8 [H*W,3])
+    pair.  A frame whose camera misses the box (`count == 0`) launches nothing but the paint."""
+    from . import ops
+    H, W = int(frame["img_height"]), int(frame["img_width"])
+    slot, n = frame["slot"], int(frame["count"])
+    dev = slot.device
+    bgcolor = frame["bgcolor"]
+    rgb = acc = depth = None
+    if n > 0:
+        per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
+        per_frame["is_train"] = False
+        with evaluating(hos):
+            pro = hos.human.frame_prologue(**per_frame)
+            out = hos.human(rays=frame["rays"], near=frame["near"], far=frame["far"], prologue=pro, with_cycle=False, **per_frame)
+            rgb, acc, _, depth = ops.raw2outputs(out["human_rgbsigma"], out["z_vals"], out["rays_d"], out["pts_mask"],
+                                                 torch.as_tensor(bgcolor, dtype=torch.float32, device=dev))
+    rendered, u8 = rays_mod.paint_frame(slot, rgb, bgcolor, H, W, want_u8=want_u8)
+    if maps:
+        zero = torch.zeros(3, device=dev)
+        flat = lambda x: None if x is None else x[:, None].expand(-1, 3)
+        rendered = {"rgb": rendered, "alpha": rays_mod.paint_frame(slot, flat(acc), zero, H, W, want_u8=False)[0][:, 0].contiguous(),
+                    "depth": rays_mod.paint_frame(slot, flat(depth), zero, H, W, want_u8=False)[0][:, 0].contiguous()}
+    return (rendered, u8) if want_u8 else rendered
+
+
 def psnr_metric(img_pred: torch.Tensor, img_gt: torch.Tensor) -> float:
     """M:101-112: -10 log10(mean squared error) over the whole frame, images in [0, 1]."""
     mse = torch.mean((img_pred.double() - img_gt.double()) ** 2).item()

@@ -6,7 +6,7 @@ arrays through pinned memory every step."""
 from __future__ import annotations
 
 import ctypes
-from typing import Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -68,6 +68,66 @@ def rays_intersect_3d_bbox(bounds, ray_o: torch.Tensor, ray_d: torch.Tensor):
     call("hos_rays_aabb", ptr(ray_o), ptr(ray_d), n, bp, ptr(near), ptr(far), mask.data_ptr())
     m = mask.bool()
     return near[m], far[m], m
+
+
+# ------------------------------------------------------------------------------------------ human-only frames
+FRAME_BLOCK = 256          # pixels per workgroup of hos_frame_rays_compact (FR_BLOCK in hos_rays.hip): sizes its scratch
+
+
+def frame_rays_compact(H: int, W: int, K, R, T, bounds, device="cuda") -> Dict[str, torch.Tensor]:
+    """`get_rays_from_KRT` + `rays_intersect_3d_bbox` + the boolean indexing of a dataset's `__getitem__`
+    (core/data/human_nerf/tpose.py:173-185) as ONE entry, hos_frame_rays_compact: the rays of one camera that hit one box, in
+    pixel order (the order of `ray_mask.nonzero()`), bit for bit what the two separate entries give.
+
+    Returns `rays_o`, `rays_d` [count,3], `near`, `far` [count] (views of the first `count` rows of H*W-row buffers), `pix`
+    [count] int32 (the pixel of each ray), `slot` [H*W] int32 (the position of each pixel in the list, -1 where the ray misses
+    the box) and `count` (int).  ONE `.item()` per frame -- the read-back of `count`, which sizes everything downstream -- is the
+    only host synchronisation; the composition it replaces pays a `nonzero` per indexed tensor."""
+    if isinstance(bounds, dict):
+        bounds = np.stack([np.asarray(bounds["min_xyz"]), np.asarray(bounds["max_xyz"])], axis=0)
+    T = np.asarray(T.detach().cpu() if isinstance(T, torch.Tensor) else T).reshape(3)
+    Kinv = np.linalg.inv(_host3(K, (3, 3)))               # 3x3 inverse on the host, like the reference (C:178)
+    k32, kp = _fptr(Kinv)
+    r32, rp = _fptr(_host3(R, (3, 3)))
+    t32, tp = _fptr(_host3(T, (3,)))
+    b32, bp = _fptr(np.asarray(bounds, dtype=np.float64).reshape(6))
+    dev = torch.device(device)
+    n = H * W
+    o = torch.empty(n, 3, device=dev)
+    d = torch.empty(n, 3, device=dev)
+    near = torch.empty(n, device=dev)
+    far = torch.empty(n, device=dev)
+    ints = torch.empty(2 * n + 1 + (n + FRAME_BLOCK - 1) // FRAME_BLOCK, dtype=torch.int32, device=dev)
+    pix, slot, count, ws = ints[:n], ints[n:2 * n], ints[2 * n:2 * n + 1], ints[2 * n + 1:]
+    call("hos_frame_rays_compact", kp, rp, tp, bp, H, W, ptr(o), ptr(d), ptr(near), ptr(far), ptr(pix, torch.int32),
+         ptr(slot, torch.int32), ptr(count, torch.int32), ptr(ws, torch.int32))
+    c = int(count.item())                                  # the frame's one host synchronisation (keeps k32 .. b32 alive past the launch)
+    return {"rays_o": o[:c], "rays_d": d[:c], "near": near[:c], "far": far[:c], "pix": pix[:c], "slot": slot, "count": c}
+
+
+def paint_frame(slot: torch.Tensor, rgb: Optional[torch.Tensor], bgcolor, H: int, W: int, want_u8: bool = True,
+                want_f32: bool = True):
+    """`rendered = full(bgcolor / 255); rendered[ray_mask] = rgb` (src/model/mipnerf360/model.py:610-612, :627) and
+    `to_8b_image(rendered)` (:629) in one launch, hos_frame_paint.  `slot` [H*W] int32 from `frame_rays_compact`, `rgb`
+    [count, 3] (None / empty for a frame without rays), `bgcolor` in 0..255.  Returns (float frame [H*W,3] or None, 8-bit frame
+    [H*W,3] uint8 or None)."""
+    dev = slot.device
+    if slot.numel() != H * W:
+        raise ValueError(f"slot has {slot.numel()} entries for a {H} x {W} frame")
+    if not (want_u8 or want_f32):
+        raise ValueError("paint_frame: nothing asked for")
+    bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev).reshape(3) / 255.0           # as eval.render_frame forms it
+    if rgb is not None and rgb.shape[0] == 0:
+        rgb = None
+    if rgb is not None:
+        if rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise ValueError(f"rgb must be [count, 3], got {tuple(rgb.shape)}")
+        rgb = rgb.contiguous()
+    out = torch.empty(H * W, 3, device=dev) if want_f32 else None
+    out8 = torch.empty(H * W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    call("hos_frame_paint", ptr(slot, torch.int32), ptr(rgb), 0 if rgb is None else int(rgb.shape[0]), ptr(bg), H, W, ptr(out),
+         0 if out8 is None else out8.data_ptr())
+    return out, out8
 
 
 # ------------------------------------------------------------------------------------------ training item: patches

@@ -262,6 +262,23 @@ int hos_camera_rays(const float* Kinv9, const float* R9, const float* T3, int H,
 int hos_rays_aabb(const float* rays_o, float* rays_d, int64_t n, const float* bounds6, float* near, float* far,
                   unsigned char* mask, hos_stream_t stream);
 
+/* hos_camera_rays followed by hos_rays_aabb for ONE camera and ONE box, keeping only the rays that hit the box, in pixel order
+ * (the order of ray_mask.nonzero()): the ray part of a human-only frame (core/data/human_nerf/tpose.py:168-185).  cap = H*W:
+ * rays_o / rays_d [cap,3], near / far [cap], pix [cap] (pixel of each kept ray) -- only the first `count` rows are written;
+ * slot [H*W] = position of each pixel in the list or -1; count [1] on the device; ws [ceil(H*W / 256)] int32 device scratch
+ * (per-block counts, then their exclusive scan).  The kept rays_d carry the 1e-5 clamp of C:238.  Three launches ordered by the
+ * stream (count, scan, write); the order never depends on scheduling.  H*W must stay below 2^31 - 256 (HOS_E_SHAPE). */
+int hos_frame_rays_compact(const float* Kinv9, const float* R9, const float* T3, const float* bounds6, int H, int W,
+                           float* rays_o, float* rays_d, float* near, float* far, int32_t* pix, int32_t* slot,
+                           int32_t* count, int32_t* ws, hos_stream_t stream);
+
+/* The frame of a ray list: out_f32[p] = 0 <= slot[p] < count ? rgb[slot[p]] : bg01 (`rendered[ray_mask] = rgb` over the background colour,
+ * src/model/mipnerf360/model.py:610-612, :627) and out_u8[p] = (uint8)(255 * clamp(out_f32[p], 0, 1)) (to_8b_image, :629:
+ * truncation).  rgb [count,3] (NULL when count == 0: a camera that misses the box), bg01 [3] DEVICE floats = bgcolor / 255, out_f32 / out_u8
+ * [H*W,3]; either output may be NULL, not both. */
+int hos_frame_paint(const int32_t* slot, const float* rgb, int count, const float* bg01, int H, int W, float* out_f32,
+                    unsigned char* out_u8, hos_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * ConvTranspose3d(kernel 4, stride 2, padding 1) of the motion-weight volume decoder (network_util.py:21-59,
  * deconv_vol_decoder.py:17-42) = GEMM (hos_linear_*) + these two gathers; activations are channel-last [voxel][C].

@@ -5,7 +5,9 @@
 hosnerf`), `run.max_steps`, `run.grad_max_norm`, `run.bkgd_path` / `run.human_path` (stage-3 warm start, run.py:206-212),
 `run.run_train`, `run.run_eval` (S3/run.py:224-231 -> `trainer.test`: the held-out frames rendered by their own cameras, PSNR,
 `test_metrics`, M:884-1085) and `run.run_render` (S3/run.py:233-239 -> `trainer.predict`: the free-viewpoint turn about the subject
-of `freeview.frame_idx`, `free_view`, M:1293-1494, cameras of core/utils/camera_util.py:106-131), both from `last.ckpt` (stage 3).
+of `freeview.frame_idx`, `free_view`, M:1293-1494, cameras of core/utils/camera_util.py:106-131), both from `last.ckpt` (stage 3), and `run.run_tpose` (this build's
+binding for the last output of the reference's `test_step`, `test_tpose`, M:591-658: the canonical human-object in T-pose, no background, one
+`--render_frames` turn per object state).
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -61,8 +63,8 @@ def parse_args(argv=None):
                    "poses_bounds.npy, mesh_infos.pkl, canonical_joints.pkl, images/, masks/, images_flow/): training items, evaluation "
                    "frames and free-viewpoint frames are built from it on the device (stages 2 / 3)")
     p.add_argument("--eval_skip", type=int, default=0, help="run_eval: render every eval_skip-th frame of the scene (default: 8 frames spread over the sequence)")
-    p.add_argument("--render_frames", type=int, default=100, help="run_render: cameras per free-viewpoint turn (cfg.render_frames)")
-    p.add_argument("--render_limit", type=int, default=0, help="run_render: stop after this many cameras of the turn (0 = all)")
+    p.add_argument("--render_frames", type=int, default=100, help="run_render / run_tpose: cameras per turn (cfg.render_frames)")
+    p.add_argument("--render_limit", type=int, default=0, help="run_render / run_tpose: stop after this many cameras of a turn (0 = all)")
     return p.parse_args(argv)
 
 
@@ -295,29 +297,33 @@ def run(args, gin):
             import torch.distributed as dist
             dist.barrier()              # the other ranks' evaluation reads the checkpoint rank 0 has just written
     result = {"exp_name": exp_name, "checkpoint": ckpt}
-    run_eval, run_render = bool(kw.get("run_eval", False)), bool(kw.get("run_render", False))
-    if run_eval or run_render:
-        result.update(evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval, run_render))
+    run_eval, run_render, run_tpose = bool(kw.get("run_eval", False)), bool(kw.get("run_render", False)), bool(kw.get("run_tpose", False))
+    if run_eval or run_render or run_tpose:
+        result.update(evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, run_tpose))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
     return result
 
 
-def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool):
+def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool,
+                        run_tpose: bool = False):
     """`trainer.test` / `trainer.predict` of the stage-3 launcher (S3/run.py:224-239) from `last.ckpt`: `test_metrics` over held-out
     frames (PSNR against the frame's pixels, images under <logdir>/test_vis) and `free_view` over the orbit cameras of
     `freeview.frame_idx` (images under <logdir>/freeview_vis_newtrans/view_<idx>), every frame through `eval.render_frame`; with
-    several ranks each frame's rays are split over the group.  Writes <logdir>/results.json."""
+    several ranks each frame's rays are split over the group.  `run_tpose` (`test_tpose`, M:591-658, the last output of the reference's
+    `test_step`): the canonical human-object in T-pose without background, one turn of `--render_frames` cameras per object state,
+    through `eval.render_human_frame`, images under <logdir>/tpose_vis/time_<t>; with several ranks the FRAMES are dealt round-robin
+    (no collectives).  Writes <logdir>/results.json."""
     from hosnerf_amd import eval as ev, select_option
     from hosnerf_amd.freeview import save_image, save_maps
     render_maps = bool(kw.get("render_maps", False))          # run.render_maps: depth / opacity / human-layer files next to each frame
     if model_name != "hosnerf":
-        raise SystemExit("run.run_eval / run.run_render: full-frame rendering is the stage-3 (`hosnerf`) launcher's; stages 1 / 2 report their training loss only")
+        raise SystemExit("run.run_eval / run.run_render / run.run_tpose: full-frame rendering is the stage-3 (`hosnerf`) launcher's; stages 1 / 2 report their training loss only")
     if scene is None:
-        raise SystemExit("run.run_eval / run.run_render need --scene_dir (frames, cameras and SMPL fits to render)")
+        raise SystemExit("run.run_eval / run.run_render / run.run_tpose need --scene_dir (frames, cameras and SMPL fits to render)")
     if not os.path.exists(ckpt):
-        raise SystemExit(f"run.run_eval / run.run_render: {ckpt} does not exist (train first, or pass --ckpt_path)")
+        raise SystemExit(f"run.run_eval / run.run_render / run.run_tpose: {ckpt} does not exist (train first, or pass --ckpt_path)")
     select_option.load_checkpoint(lit, ckpt, strict=True)
     hos = lit.net                                   # the composite renderer that owns `model` and `human`
     group = None
@@ -362,10 +368,41 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         out["freeview"] = {"frame_idx": fidx, "frames": count, "of": total, "psnr_vs_training_frame": float(sum(psnrs) / len(psnrs))}
         if rank == 0:
             print(f"[run] Freeview: {count} of {total} cameras about frame {fidx} written to {os.path.join(logdir, 'freeview_vis_newtrans')}")
+    if run_tpose:
+        out["tpose"] = render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps)
     if rank == 0:
         with open(os.path.join(logdir, "results.json"), "w") as f:
             json.dump(out, f, indent=1)
     return {"results": out}
+
+
+def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps: bool):
+    """`test_tpose` for every time of `tpose.tpose_times` (M:643-658): `--render_frames` cameras per turn (`--render_limit` stops a
+    turn early), rank r renders the frames k % world == r and writes its own files -- <logdir>/tpose_vis/time_{:06}/image-{:05}.jpg
+    (M:631-635) from the paint kernel's 8-bit buffer and, with `run.render_maps`, <name>_alpha.png."""
+    from PIL import Image
+    from hosnerf_amd import eval as ev, tpose
+    total = int(args.render_frames)
+    count = min(total, args.render_limit) if args.render_limit > 0 else total
+    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
+    step = float(ck["global_step"]) if isinstance(ck, dict) and "global_step" in ck else 1e7      # M:615; a bare state_dict: as the other frames
+    del ck
+    turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
+    times = tpose.tpose_times(hos.human.transitions_times)
+    for t in times:
+        for k in range(rank, count, world):
+            folder, name = tpose.tpose_paths(t, k)
+            fr = tpose.tpose_frame(None, None, k, total, bgcolor=bgc, turn=turn, iter_val=step, time=t)
+            rendered, u8 = ev.render_human_frame(hos, fr, maps=render_maps, want_u8=True)
+            H, W = int(fr["img_height"]), int(fr["img_width"])
+            os.makedirs(os.path.join(logdir, "tpose_vis", folder), exist_ok=True)
+            Image.fromarray(u8.view(H, W, 3).cpu().numpy()).save(os.path.join(logdir, "tpose_vis", folder, name))
+            if render_maps:
+                alpha8 = ev.to_8b_image(rendered["alpha"].view(H, W)).cpu().numpy()
+                Image.fromarray(alpha8).save(os.path.join(logdir, "tpose_vis", folder, os.path.splitext(name)[0] + "_alpha.png"))
+    if rank == 0:
+        print(f"[run] T-pose: {count} of {total} cameras for each of {len(times)} states written to {os.path.join(logdir, 'tpose_vis')}")
+    return {"times": times, "frames": count, "of": total}
 
 
 def main(argv=None):
