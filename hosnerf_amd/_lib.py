@@ -64,6 +64,9 @@ PROTOTYPES = {
     "hos_rays_aabb": [_P, _P, _L, _P, _P, _P, _P, _P],
     "hos_frame_rays_compact": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hos_frame_paint": [_P, _P, _I, _P, _I, _I, _P, _P, _P],
+    "hos_raybank_index": [_P, _I, _I, _I, _P, _L, _P, _P, _P, _P],
+    "hos_raybank_gather": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P],
+    "hos_raybank_frame": [_P, _F, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P],
     "hos_deconv3d_col2im": [_P, _P, _I, _I, _F, _I, _P, _P],
     "hos_deconv3d_im2col": [_P, _I, _I, _P, _P],
     "hos_bias_lrelu": [_P, _P, _L, _I, _F, _I, _P],

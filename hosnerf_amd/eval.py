@@ -191,6 +191,59 @@ def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = Fal
     return (rendered, u8) if want_u8 else rendered
 
 
+def render_bkgd_frame(model, bank, frame_or_pose, chunk: int, train_frac: float, near: float, far: float) -> torch.Tensor:
+    """One whole frame of the stage-1 background model, the loop of `trainer.test` / `trainer.predict` over `render_rays`
+    (1st_State-Conditional_Scene/src/model/mipnerf360/model.py:516-534): for each `chunk` (= `LitData.chunk`) rays of the frame,
+    `model(batch, train_frac, False, False, near, far)` and the last level's colour.  `model` is the `MipNeRF360`, `bank` a
+    `raybank.RayBank`; `frame_or_pose` is a scene image index i (`bank.frame`: its own camera, time and pixels) or `("pose", k)`
+    (`bank.render_pose`: camera k of the render path).  Returns [H*W,3] on the device.
+
+    `randomized=False` reaches the resampling kernel (no jitter: bin centres, `sample_intervals`), the only place the reference's
+    forward uses it with its shipped configuration (density / bottleneck noise are 0 and refused otherwise by `MipNeRF360MLP`);
+    `is_train=False` only selects how the reference evaluates the contraction's Jacobian (helper.py:40-52, the same numbers), so
+    the model needs nothing further for this mode.  No autograd, and the module's training flag is left as it was."""
+    if isinstance(frame_or_pose, tuple):
+        kind, idx = frame_or_pose
+        if kind not in ("frame", "pose"):
+            raise ValueError(f"frame_or_pose: {frame_or_pose!r}")
+    else:
+        kind, idx = "frame", frame_or_pose
+    rays = bank.frame if kind == "frame" else bank.render_pose
+    n = bank.H * bank.W
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    parts = []
+    with torch.no_grad():
+        for start in range(0, n, chunk):
+            batch = rays(int(idx), start, min(chunk, n - start))
+            rend, _ = model(batch, train_frac, False, False, near, far)
+            parts.append(rend[-1]["rgb"])
+    return torch.cat(parts, 0)
+
+
+def psnr_each(img_pred: torch.Tensor, img_gt: torch.Tensor) -> float:
+    """`psnr_each` of the stage-1 launcher (1st_State-Conditional_Scene/src/model/interface.py:42-50) for one image: both clipped to
+    0..1, then -10 log10(mean squared error)."""
+    mse = torch.mean((img_pred.double().clamp(0.0, 1.0) - img_gt.double().clamp(0.0, 1.0)) ** 2).item()
+    return -10.0 * math.log(mse) / math.log(10.0)
+
+
+def bkgd_results(psnrs) -> Dict[str, Dict[str, float]]:
+    """What `write_stats` (interface.py:121-132) leaves in results.json for `eval_test_only` (:77-89), PSNR only: SSIM and LPIPS
+    are not computed for stage 1 and are not mentioned."""
+    mean = float(np.mean(np.asarray(psnrs, dtype=np.float64)))
+    return {"PSNR": {"mean": mean, "test": mean}}
+
+
+def write_bkgd_results(path: str, psnrs) -> Dict[str, Dict[str, float]]:
+    import json
+    d = bkgd_results(psnrs)
+    with open(path, "w") as fp:
+        json.dump(d, fp, indent=4, sort_keys=True)          # interface.py:131-132
+    return d
+
+
 def psnr_metric(img_pred: torch.Tensor, img_gt: torch.Tensor) -> float:
     """M:101-112: -10 log10(mean squared error) over the whole frame, images in [0, 1]."""
     mse = torch.mean((img_pred.double() - img_gt.double()) ** 2).item()

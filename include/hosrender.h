@@ -280,6 +280,38 @@ int hos_frame_paint(const int32_t* slot, const float* rgb, int count, const floa
                     unsigned char* out_u8, hos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stage-1 ray bank (1st_State-Conditional_Scene/src/data/interface.py:105-296 over ray_utils.py:34-139): the training rays of a
+ * scene without the reference's host table.  Device-resident, uploaded once: images uint8 [N,H,W,3], keep uint8 [N,H,W]
+ * (= mask < 1), cams [N,16] fp32 (camera-to-world 3x4 row-major, then fx, fy, cx, cy), times [N].  A ray is rebuilt from its
+ * pixel: dir = ((col + 0.5 - cx) / fx, (row + 0.5 - cy) / fy, 1), rays_d = viewdirs = R dir / |R dir| (the reference normalises
+ * rays_d in place, ray_utils.py:87-88), rays_o = the camera centre, radii = |R e_y| / fy * 2 / sqrt(12) (closed form of the
+ * row difference, :96-108), target = (float)u8 / 255.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Once per scene: per image the pixels with keep != 0 in pixel order (the order of `_rays_o[masks_idx]`), as int32 written to
+ * pix at a running 64-bit offset; counts [N] (= bkgrays_sizes) and offsets [N+1] (exclusive scan of counts, offsets[N] = total).
+ * cap = rows of pix (nothing is written past them); ws [N * ceil(H*W / 256)] int32 device scratch.  Three launches ordered by the
+ * stream (per-block counts, a scan by one workgroup, write).  H*W must stay below 2^31 - 256 and N * ceil(H*W / 256) below 2^31
+ * (HOS_E_SHAPE). */
+int hos_raybank_index(const unsigned char* keep, int N, int H, int W, int32_t* pix, int64_t cap, int32_t* counts,
+                      int64_t* offsets, int32_t* ws, hos_stream_t stream);
+
+/* Per step: ray r is pixel pix[offsets[img_id[r]] + rank[r]] of image img_id[r].  rays_o, rays_d, viewdirs, target [B,3], radii
+ * [B] (= [B,1]), times_out [B].  A pair outside the bank (img_id not in [0,N), rank not in [0,counts[img])) reads nothing and
+ * gives a NaN row.  B = 0 launches nothing. */
+int hos_raybank_gather(const float* cams, const float* times, const unsigned char* images, const int32_t* pix,
+                       const int64_t* offsets, const int32_t* counts, const int32_t* img_id, const int32_t* rank,
+                       int64_t B, int N, int H, int W, int64_t cap, float* rays_o, float* rays_d, float* viewdirs,
+                       float* radii, float* times_out, float* target, hos_stream_t stream);
+
+/* The same per-pixel functions for the pixels [start, start + n) of ONE camera (cam16: 16 HOST floats, passed to the kernel by
+ * value) at one time: whole test frames and render-path cameras, no mask (`split_each_val`).  image [H*W,3] uint8 (device) and
+ * target [n,3] go together; both NULL for a camera without pixels (the render path).  n = 0 launches nothing. */
+int hos_raybank_frame(const float* cam16, float time, int H, int W, int64_t start, int64_t n, const unsigned char* image,
+                      float* rays_o, float* rays_d, float* viewdirs, float* radii, float* times_out, float* target,
+                      hos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTranspose3d(kernel 4, stride 2, padding 1) of the motion-weight volume decoder (network_util.py:21-59,
  * deconv_vol_decoder.py:17-42) = GEMM (hos_linear_*) + these two gathers; activations are channel-last [voxel][C].
  * ------------------------------------------------------------------------------------------ */

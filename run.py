@@ -7,7 +7,9 @@ hosnerf`), `run.max_steps`, `run.grad_max_norm`, `run.bkgd_path` / `run.human_pa
 `test_metrics`, M:884-1085) and `run.run_render` (S3/run.py:233-239 -> `trainer.predict`: the free-viewpoint turn about the subject
 of `freeview.frame_idx`, `free_view`, M:1293-1494, cameras of core/utils/camera_util.py:106-131), both from `last.ckpt` (stage 3), and `run.run_tpose` (this build's
 binding for the last output of the reference's `test_step`, `test_tpose`, M:591-658: the canonical human-object in T-pose, no background, one
-`--render_frames` turn per object state).
+`--render_frames` turn per object state).  Stage 1 (`state_mipnerf360`) with `--scene_dir`: training batches from the scene's unmasked pixels
+(`raybank.RayBank.sample`, the reference's `SingleImageDDPSampler`), `run.run_eval` -> the test split's whole frames under
+<logdir>/render_model + results.json (PSNR), `run.run_render` -> the interpolated camera path under <logdir>/render_video.
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -61,7 +63,8 @@ def parse_args(argv=None):
     p.add_argument("--rays", type=int, default=0, help="rays per step and GPU for synthetic items (default: the stage's reference batch)")
     p.add_argument("--scene_dir", type=str, default=None, help="scene directory in the reference's on-disk formats (cameras.pkl / "
                    "poses_bounds.npy, mesh_infos.pkl, canonical_joints.pkl, images/, masks/, images_flow/): training items, evaluation "
-                   "frames and free-viewpoint frames are built from it on the device (stages 2 / 3)")
+                   "frames and free-viewpoint frames are built from it on the device (stages 2 / 3); stage 1 trains on its unmasked "
+                   "pixels (a device-resident ray bank), evaluates its test split and renders its camera path")
     p.add_argument("--eval_skip", type=int, default=0, help="run_eval: render every eval_skip-th frame of the scene (default: 8 frames spread over the sequence)")
     p.add_argument("--render_frames", type=int, default=100, help="run_render / run_tpose: cameras per turn (cfg.render_frames)")
     p.add_argument("--render_limit", type=int, default=0, help="run_render / run_tpose: stop after this many cameras of a turn (0 = all)")
@@ -237,10 +240,16 @@ def run(args, gin):
         for n, it in enumerate(items):
             if "patch_masks" in it and not bool(torch.as_tensor(it["patch_masks"]).all()):
                 raise SystemExit(f"--items[{n}]: patch_masks has holes; stage 3 takes whole patches (the reference's stage-3 _unpack_imgs is a reshape)")
-    scene = None
-    if args.scene_dir:
-        if model_name == "state_mipnerf360":
-            raise SystemExit("--scene_dir builds human-object items (stages 2 / 3); stage 1 takes --items or synthetic rays")
+    scene = bank = None
+    if args.scene_dir and model_name == "state_mipnerf360":
+        # stage 1: the scene's unmasked pixels as a device-resident ray bank (hosnerf_amd/raybank.py) -- the role of LitData.split_each +
+        # SingleImageDDPSampler (S1/src/data/interface.py:105-205, sampler.py:52-101) without the host ray table
+        bank = load_ray_bank(args.scene_dir, dev, lit.near, lit.far)
+        bank_gen = torch.Generator(device=dev)
+        bank_gen.manual_seed(args.seed)                  # the SAME seed on every rank: a step's draw is shared, each rank keeps [rank::world]
+        print(f"[run] scene {args.scene_dir}: {bank.N} frames of {bank.W}x{bank.H}, {int(bank.offsets_host[-1])} unmasked rays, "
+              f"{len(bank.choice_host)} of {len(bank.split)} training images with rays, {len(bank.i_test)} test frames")
+    elif args.scene_dir:
         from hosnerf_amd import formats
         from hosnerf_amd.dataset import SceneItems
         from hosnerf_amd.freeview import load_scene_pixels
@@ -268,7 +277,9 @@ def run(args, gin):
 
     if run_train:
         for step in range(step0, max_steps):
-            if scene is not None:
+            if bank is not None:
+                item = bank.sample(rays * world, bank_gen, rank, world)        # LitData.batch_size rays of ONE image; this rank's [rank::world]
+            elif scene is not None:
                 item = scene[int(torch.randint(len(scene), (1,)))] if len(scene) > 1 else scene[0]      # shuffled frames (DataLoader(shuffle=True))
             else:
                 item = items[step % len(items)] if items else synthetic_item(model_name, rays, args.seed + 1000 * rank, step)
@@ -299,15 +310,86 @@ def run(args, gin):
     result = {"exp_name": exp_name, "checkpoint": ckpt}
     run_eval, run_render, run_tpose = bool(kw.get("run_eval", False)), bool(kw.get("run_render", False)), bool(kw.get("run_tpose", False))
     if run_eval or run_render or run_tpose:
-        result.update(evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, run_tpose))
+        result.update(evaluate_and_render(args, kw, lit, model_name, scene if bank is None else bank, ckpt, logdir, dev, rank, world, run_eval,
+                                          run_render, run_tpose, bkgd_chunk=int(gin.get_param("LitData.chunk", 1024 * 32))))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
     return result
 
 
+def load_ray_bank(scene_dir: str, dev, near: float, far: float):
+    """Decode a scene directory and build the stage-1 `RayBank`: `formats.load_scene` (normalised cameras, splits, render path,
+    `bkgrays_sizes`; writes cameras_scaleworld.pkl for the later stages like the reference's loader) over `freeview.load_scene_pixels`."""
+    from hosnerf_amd import formats
+    from hosnerf_amd.freeview import load_scene_pixels
+    from hosnerf_amd.raybank import RayBank
+    px = load_scene_pixels(scene_dir)
+    scene = formats.load_scene(scene_dir, px["images"].shape[1:3], masks=px["alphas"], near=near, far=far)
+    split = "train"
+    if len(scene["i_split"][0]) == 0:
+        # fewer than 16 frames: `load_scene` holds every frame out as a test frame (the reference needs >= 16 frames); such a scene
+        # trains on the frames it has
+        print(f"[run] {scene_dir}: every frame is a test frame (fewer than 16 frames); training draws from all of them")
+        split = "all"
+    return RayBank(scene, px["images"], px["alphas"], device=dev, split=split)
+
+
+def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool, chunk: int):
+    """`trainer.test` / `trainer.predict` of the stage-1 launcher (S1/run.py, S1/src/model/mipnerf360/model.py:516-534, :582-609,
+    S1/src/model/interface.py:137-150) from `last.ckpt`: the whole frames of the test split `i_test` through `eval.render_bkgd_frame`
+    -> <logdir>/render_model/image{NNN}.jpg + <logdir>/results.json (PSNR as `psnr_each`; SSIM / LPIPS are not computed), and the
+    cameras of the interpolated path `render_poses` / `render_times` -> <logdir>/render_video/image{NNN}.jpg (`--render_limit` stops
+    early; no mp4).  `train_frac` is the checkpoint's global_step / run.max_steps.  With several ranks the FRAMES are dealt
+    round-robin (as `render_tpose`), each rank writes its own files, and one all-reduce of the per-frame PSNR vector precedes rank
+    0's results.json."""
+    from PIL import Image
+    from hosnerf_amd import eval as ev, select_option
+    from hosnerf_amd.raybank import deal_frames
+    if bank is None:
+        raise SystemExit("run.run_eval / run.run_render need --scene_dir (frames and cameras to render)")
+    if not os.path.exists(ckpt):
+        raise SystemExit(f"run.run_eval / run.run_render: {ckpt} does not exist (train first, or pass --ckpt_path)")
+    select_option.load_checkpoint(lit, ckpt, strict=True)
+    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
+    step = int(ck["global_step"]) if isinstance(ck, dict) and "global_step" in ck else int(lit.max_steps)
+    del ck
+    train_frac = step / max(int(lit.max_steps), 1)
+    H, W = bank.H, bank.W
+
+    def write(folder, k, rendered):
+        os.makedirs(os.path.join(logdir, folder), exist_ok=True)
+        Image.fromarray(ev.to_8b_image(rendered.view(H, W, 3)).cpu().numpy()).save(os.path.join(logdir, folder, f"image{str(k).zfill(3)}.jpg"))
+
+    out = {}
+    if run_eval:
+        frames = [int(i) for i in bank.i_test]
+        psnrs = torch.zeros(len(frames), dtype=torch.float64)
+        for j in deal_frames(len(frames), rank, world):
+            rendered = ev.render_bkgd_frame(lit.model, bank, frames[j], chunk, train_frac, lit.near, lit.far)
+            psnrs[j] = ev.psnr_each(rendered, bank.truth(frames[j]))
+            write("render_model", j, rendered)
+        if world > 1:
+            import torch.distributed as dist
+            if dist.get_backend() == "nccl":
+                psnrs = psnrs.to(dev)
+            dist.all_reduce(psnrs)                       # every frame was rendered by exactly one rank: the sum is the vector
+            psnrs = psnrs.cpu()
+        if rank == 0:
+            out.update(ev.write_bkgd_results(os.path.join(logdir, "results.json"), psnrs.numpy()))
+            print(f"[run] Test PSNR is {out['PSNR']['test']:.4f} over {len(frames)} frames")
+    if run_render:
+        total = len(bank.render_poses)
+        count = min(total, args.render_limit) if args.render_limit > 0 else total
+        for k in deal_frames(count, rank, world):
+            write("render_video", k, ev.render_bkgd_frame(lit.model, bank, ("pose", k), chunk, train_frac, lit.near, lit.far))
+        if rank == 0:
+            print(f"[run] Render path: {count} of {total} cameras written to {os.path.join(logdir, 'render_video')}")
+    return {"results": out}
+
+
 def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool,
-                        run_tpose: bool = False):
+                        run_tpose: bool = False, bkgd_chunk: int = 1024 * 32):
     """`trainer.test` / `trainer.predict` of the stage-3 launcher (S3/run.py:224-239) from `last.ckpt`: `test_metrics` over held-out
     frames (PSNR against the frame's pixels, images under <logdir>/test_vis) and `free_view` over the orbit cameras of
     `freeview.frame_idx` (images under <logdir>/freeview_vis_newtrans/view_<idx>), every frame through `eval.render_frame`; with
@@ -318,8 +400,12 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     from hosnerf_amd import eval as ev, select_option
     from hosnerf_amd.freeview import save_image, save_maps
     render_maps = bool(kw.get("render_maps", False))          # run.render_maps: depth / opacity / human-layer files next to each frame
+    if model_name == "state_mipnerf360":
+        if run_tpose:
+            raise SystemExit("run.run_tpose renders the human-object network (stage 3); stage 1 has run.run_eval / run.run_render")
+        return evaluate_and_render_bkgd(args, lit, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, bkgd_chunk)
     if model_name != "hosnerf":
-        raise SystemExit("run.run_eval / run.run_render / run.run_tpose: full-frame rendering is the stage-3 (`hosnerf`) launcher's; stages 1 / 2 report their training loss only")
+        raise SystemExit("run.run_eval / run.run_render / run.run_tpose: full-frame rendering is the stage-1 (`state_mipnerf360`) and stage-3 (`hosnerf`) launchers'; stage 2 reports its training loss only")
     if scene is None:
         raise SystemExit("run.run_eval / run.run_render / run.run_tpose need --scene_dir (frames, cameras and SMPL fits to render)")
     if not os.path.exists(ckpt):
