@@ -17,8 +17,6 @@
 //     LDS-DMA (global_load_lds), shared by the four waves of a workgroup; two workgroups per CU so that one's epilogue VALU
 //     work runs under the other's MFMAs.
 // Per row: 101 120 MAC x 3 products; HBM bytes per row = 768 read (E, PE) + 6 x 512 + 12 written.
-#include <stdlib.h>
-
 #include "hos_common.h"
 #include "hos_gemm_common.h"
 
@@ -113,9 +111,7 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
         const int ks = ks_of(l, FOLD);
         // byte offset of layer l's planes: 8 k-steps per earlier layer, +4 behind the skip layer, -4 behind a folded layer 0
         const int lo = (l * 8 + (l > SKIP_LAYER ? 4 : 0) - ((FOLD && l > 0) ? 4 : 0)) * 4 * 2048;
-#ifndef HOS_CHAIN_NO_DMA        // timing experiments only (results invalid)
         dma16(reinterpret_cast<const char*>(a.Wc) + lo + ob * ks * 2048 + voff + q * 4096, wbuf + parity * CBUF + wave * 1024 + q * 4096);
-#endif
     };
     auto issue_chunk = [&](int l, int ob, int parity) {
         const int rounds = ks_of(l, FOLD) / 2;
@@ -225,11 +221,7 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
                     } else {
                         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fh[0]), "+v"(fl[0]), "+v"(fh[1]), "+v"(fl[1]));
                     }
-#ifndef HOS_CHAIN_NO_MFMA
                     acc[ob] = mfma3(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
-#else
-                    acc[ob][s & 15] += (float)fh[s & 1][0] + (float)fl[s & 1][1];
-#endif
                     if ((s & 1) == 0 && (s >> 1) < nrounds) issue_round(nl, nob, npar, s >> 1);
                 }
                 if (ks == 12) {
@@ -244,11 +236,7 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
                         } else {
                             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fh[0]), "+v"(fl[0]), "+v"(fh[1]), "+v"(fl[1]));
                         }
-#ifndef HOS_CHAIN_NO_MFMA
                         acc[ob] = mfma3(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
-#else
-                        acc[ob][s & 15] += (float)fh[s & 1][0] + (float)fl[s & 1][1];
-#endif
                         if ((s & 1) == 0 && (s >> 1) < nrounds) issue_round(nl, nob, npar, s >> 1);
                     }
                 }
@@ -274,12 +262,10 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
                         v[4 * u + 1] = fmaxf(acc[ob][4 * q + 1] + b4.y, 0.f);
                         v[4 * u + 2] = fmaxf(acc[ob][4 * q + 2] + b4.z, 0.f);
                         v[4 * u + 3] = fmaxf(acc[ob][4 * q + 3] + b4.w, 0.f);
-#ifndef HOS_CHAIN_NO_STORE
                         // (a lane owns ONE row here, so a store instruction touches 32 lines; staging the block through LDS for
                         // whole-line stores was measured no faster: the stores are bound by the HBM write rate -- 3 KB per row --
                         // and all CUs reach their epilogues at the same time)
                         if (row < P) *reinterpret_cast<float4*>(out + n0) = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
-#endif
                         if (last) {
                             const float* w6 = s_aux + NL * CW + 4 * hh;
 #pragma unroll
@@ -408,10 +394,7 @@ extern "C" int hos_mlp_chain_pack_fold(const float* const* weights7, const int* 
 
 template <bool FOLD>
 static int chain128_launch(const ChainArgs& a, hipStream_t stream) {
-    // HOS_CHAIN_LDS_PAD (diagnostic): extra dynamic LDS per workgroup, e.g. 26000 -> two workgroups own a CU's whole LDS and no
-    // other kernel's workgroup can become co-resident on it
-    static const size_t pad = getenv("HOS_CHAIN_LDS_PAD") ? (size_t)atoi(getenv("HOS_CHAIN_LDS_PAD")) : 0;
-    const size_t smem = SMEM_BYTES + pad;
+    const size_t smem = SMEM_BYTES;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain128_kernel<FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -419,8 +402,7 @@ static int chain128_launch(const ChainArgs& a, hipStream_t stream) {
         attr_set = true;
     }
     const long ntiles = (a.P + CROWS - 1) / CROWS;
-    static int max_grid = 0;
-    if (max_grid == 0) { const char* e = getenv("HOS_CHAIN_GRID"); max_grid = e ? atoi(e) : 1024; if (max_grid <= 0) max_grid = 1024; }
+    constexpr int max_grid = 1024;
     const int grid = (int)(ntiles < max_grid ? ntiles : max_grid);
     hipLaunchKernelGGL(chain128_kernel<FOLD>, dim3(grid), dim3(CT), smem, stream, a);
     return hos_launch_status();

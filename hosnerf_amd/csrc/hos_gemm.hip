@@ -17,7 +17,6 @@
 #include "hos_common.h"
 
 #include "hos_gemm_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -337,8 +336,7 @@ struct SplitKPlan { int tiles_m, tiles_n, splits, kt_per_split; bool few; };
 // 32-row tiles up to 64 rows and ~256 workgroups (round 3, scripts/bench_decoder.py: [64,512] from K = 16 384 39 -> 22 us,
 // [512,256] 71 -> 63 us, [4096,256] from K = 1 728 57 -> 54 us; 128 or 1024 workgroups are 25-50 % slower)
 inline SplitKPlan splitk_plan(int M, int N, int K) {
-    static const int few_max = getenv("HOS_SPLITK_FEW_M") ? atoi(getenv("HOS_SPLITK_FEW_M")) : 64;
-    static const int target = getenv("HOS_SPLITK_TARGET") ? atoi(getenv("HOS_SPLITK_TARGET")) : 256;
+    constexpr int few_max = 64, target = 256;
     SplitKPlan p;
     const int nk = K / BK;
     p.few = M <= few_max;
@@ -444,26 +442,12 @@ extern "C" int hos_linear_dgrad(const float* dY, int lddy, const float* W, int l
     if (g_gemm_mode == HOS_GEMM_BF16X3 && K > 32) return hos_gemm3_launch(a, MODE_DGRAD, 1, static_cast<hipStream_t>(stream));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // A handful of rows against a long weight stream (the volume decoder: 1..8 voxels x [1024, 32768] weights): 32-row tiles
-    // put 3 workgroups on a CU instead of 2 (the 128-row tile streamed the weights at ~0.8 TB/s).  HOS_DGRAD_SPLIT=1 also
-    // splits the reduction (atomics into a zeroed output: +1 % on a stage-2 step, but the result is no longer
-    // bit-reproducible from call to call, so it is off by default).
-    static const bool few_rows_split = getenv("HOS_DGRAD_SPLIT") && atoi(getenv("HOS_DGRAD_SPLIT")) == 1;
+    // put 3 workgroups on a CU instead of 2 (the 128-row tile streamed the weights at ~0.8 TB/s).  The reduction is NOT split
+    // (atomics into a zeroed output gained 1 % on a stage-2 step, but the result was no longer bit-reproducible from call to call).
     // (up to 64 rows as two 32-row tiles: the decoder's [64, 512] x [512, 16384] layer 46 -> 20 us against one half-empty 128-row tile)
-    static const int few_rows_max = getenv("HOS_FEWROW_M") ? atoi(getenv("HOS_FEWROW_M")) : 64;
-    if (M <= few_rows_max && !accumulate && Xact == nullptr && a.nk >= 8) {
+    if (M <= 64 && !accumulate && Xact == nullptr && a.nk >= 8) {
         a.tiles_m = hos_cdiv(M, 32); a.tiles_n = hos_cdiv(K, 128);
-        int splits = 1;
-        if (few_rows_split) {
-            splits = a.nk / 4 < 4 ? a.nk / 4 : 4;
-            if (a.tiles_n * splits < 512 && a.nk / 8 >= 2) splits = a.nk / 8 < 8 ? a.nk / 8 : 8;
-        }
-        a.kt_per_split = hos_cdiv(a.nk, splits);
-        splits = hos_cdiv(a.nk, a.kt_per_split);
-        if (splits > 1) {
-            const int rc = zero2d(dX, lddx, M, K, s);
-            if (rc != 0) return rc;
-        }
-        return launch<32, 128, MODE_DGRAD>(a, splits, s);
+        return launch<32, 128, MODE_DGRAD>(a, 1, s);
     }
     a.tiles_m = hos_cdiv(M, 128); a.tiles_n = hos_cdiv(K, 128);
     return launch<128, 128, MODE_DGRAD>(a, 1, s);

@@ -22,7 +22,6 @@
 // A 256-wide tile needs (256+BN)*128 B of L2 traffic per 3072 (BN=256) matrix cycles per SIMD = 21 B/clk/CU,
 // inside the ~56 B/clk/CU the L2 delivers; a 128x128 tile would need 42 B/clk/CU and starve.
 #include "hos_gemm_common.h"
-#include <cstdlib>
 
 // Split element type: __bf16 (8-bit exponent: safe for gradients of any magnitude, ~2^-17 relative error per
 // product) for DGRAD/WGRAD, _Float16 (11-bit mantissa: hi+lo carry 22 bits, ~2^-21 relative error -- fp32 grade)
@@ -42,6 +41,7 @@ constexpr int BM = 256;
 constexpr int BK = 32;
 constexpr int NT3 = 512;
 constexpr int ROWB = 64;          // bytes per LDS row per plane (32 bf16)
+constexpr int PF_DIST = 3;        // software L2 prefetch distance in K tiles (see `prefetch` in gemm3_kernel)
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(NT3, 2) void gemm3_kernel(const GemmArgs a) {
     //   A:  issue loads(kt+1) | MFMA(kt)          | barrier | convert+store(kt+1) | barrier
     //   B:  convert+store(kt+1)                    | barrier | issue loads(kt+2) | MFMA(kt) | barrier
     // Every wave issues its global loads right before its own MFMA phase and consumes them right after it.
-    const bool grpB = !(a.ablate & 8) && __builtin_amdgcn_readfirstlane(t >> 6) >= 4;   // ablate&8: lockstep schedule
+    const bool grpB = __builtin_amdgcn_readfirstlane(t >> 6) >= 4;
     const int l31 = lane & 31, lhi = lane >> 5;
 
     auto compute = [&](int buf) {
@@ -271,10 +271,9 @@ __global__ __launch_bounds__(NT3, 2) void gemm3_kernel(const GemmArgs a) {
     // panel is evicted by it) and a wave has only one MFMA phase (~0.6 us) between issuing a tile's loads and
     // needing them -- less than the loaded HBM latency, which made the kernel latency-bound at ~10 B/clk/CU
     // (scripts/probe/*: the same access pattern streams at 23 B/clk/CU when enough requests are in flight).
-    // Each thread therefore touches ONE dword of one 128-byte line of the tile `pf_dist` tiles ahead
+    // Each thread therefore touches ONE dword of one 128-byte line of the tile PF_DIST tiles ahead
     // (512 threads = the 256 + 256 lines of an A and a B tile); the value is only "used" by an empty asm one
-    // iteration later, so the real loads that follow find their lines in L2.  (pf_dist = 0 degenerates to touching
-    // the current, already resident tile.)
+    // iteration later, so the real loads that follow find their lines in L2.
     float pfv = 0.f;
     auto prefetch = [&](int kt) {
         const int line = t & 255;
@@ -301,7 +300,6 @@ __global__ __launch_bounds__(NT3, 2) void gemm3_kernel(const GemmArgs a) {
         }
         pfv = *p;
     };
-    const int pf = a.pf_dist;
 
     gload(kt_begin);
     sstore(0);
@@ -310,37 +308,23 @@ __global__ __launch_bounds__(NT3, 2) void gemm3_kernel(const GemmArgs a) {
 
     int buf = 0;
     const int ahead = grpB ? 2 : 1;
-    // debug timeline (HOS_GEMM_ABLATE & 16): lane 0 of every wave of tile 0 stamps s_memtime at the phase
-    // boundaries of K tiles 8..11 into a.aux (as long long[8 waves][4 iters][8 stamps])
-    const bool trace = (a.ablate & 16) && bid == 0 && lane == 0 && a.aux != nullptr;
-    long long* tr = reinterpret_cast<long long*>(a.aux);
-#define HOS_STAMP(slot) do { if (trace && kt >= kt_begin + 8 && kt < kt_begin + 12) tr[(wave * 4 + (kt - kt_begin - 8)) * 8 + (slot)] = clock64(); } while (0)
     for (int kt = kt_begin; kt < kt_end; ++kt) {
         const bool more = kt + 1 < kt_end;
-        HOS_STAMP(0);
         if (grpB) {                      // B, phase 1: convert/store its share of tile kt+1 (loaded one iteration ago)
-            if (more && !(a.ablate & 2)) sstore(buf ^ 1);
-            HOS_STAMP(1);
+            if (more) sstore(buf ^ 1);
             __syncthreads();             // B's barrier #1  <->  A's barrier #1 (the common one below)
         }
-        HOS_STAMP(2);
         asm volatile("" :: "v"(pfv));                                       // retire the previous prefetch
-        if (kt + ahead < kt_end && !(a.ablate & 1)) gload(kt + ahead);
-        prefetch(min(kt + pf, kt_end - 1));    // single call site: A fetches tile kt+1, B tile kt+2
-        HOS_STAMP(3);
-        if (!(a.ablate & 4)) compute(buf);                                  // single call site: A runs it in phase 1, B in phase 2
-        HOS_STAMP(4);
+        if (kt + ahead < kt_end) gload(kt + ahead);
+        prefetch(min(kt + PF_DIST, kt_end - 1));    // single call site: A fetches tile kt+1, B tile kt+2
+        compute(buf);                                                       // single call site: A runs it in phase 1, B in phase 2
         __syncthreads();                 // A's barrier #1 / B's barrier #2
-        HOS_STAMP(5);
         if (!grpB) {                     // A, phase 2: convert/store its share of tile kt+1
-            if (more && !(a.ablate & 2)) sstore(buf ^ 1);
-            HOS_STAMP(6);
+            if (more) sstore(buf ^ 1);
             __syncthreads();             // A's barrier #2  <->  B's barrier #2 (the common one)
         }
-        HOS_STAMP(7);
         buf ^= 1;
     }
-#undef HOS_STAMP
     // (both groups have executed exactly two barriers per iteration: no drain needed)
 
 #pragma unroll
@@ -381,8 +365,6 @@ int launch3(GemmArgs& a, int splits, hipStream_t stream) {
     a.tiles_m = hos_cdiv(a.M, BM);
     a.tiles_n = hos_cdiv(a.N, BN);
     if (MODE == MODE_WGRAD) {
-        static const int env_splits = getenv("HOS_WGRAD_SPLITS") ? atoi(getenv("HOS_WGRAD_SPLITS")) : 0;
-        if (env_splits > 0) splits = env_splits;
         if (splits <= 0) {
             const int tiles = a.tiles_m * a.tiles_n;
             splits = 256 / tiles > 0 ? 256 / tiles : 1;          // one workgroup per CU: one over costs a whole second round
@@ -402,10 +384,6 @@ int launch3(GemmArgs& a, int splits, hipStream_t stream) {
 }  // namespace
 
 int hos_gemm3_launch(GemmArgs a, int mode, int splits, hipStream_t stream) {
-    static const int ablate = getenv("HOS_GEMM_ABLATE") ? atoi(getenv("HOS_GEMM_ABLATE")) : 0;
-    a.ablate = ablate;
-    static const int pf_dist = getenv("HOS_GEMM_PF") ? atoi(getenv("HOS_GEMM_PF")) : 3;
-    a.pf_dist = pf_dist;
     const bool wide = a.N > 128;
     switch (mode) {
         case MODE_FWD:   return wide ? launch3<256, MODE_FWD, _Float16>(a, 1, stream) : launch3<128, MODE_FWD, _Float16>(a, 1, stream);
@@ -413,8 +391,7 @@ int hos_gemm3_launch(GemmArgs a, int mode, int splits, hipStream_t stream) {
         default: {
             // 256 x 128 tiles up to N = 256: a [256,256] gradient then has two tiles x 128 splits instead of one x 256
             // (half the atomic traffic at the same parallelism; same finding as hos_gemmp.hip)
-            static const int narrow_max = getenv("HOS_WGRAD_NARROW_MAX") ? atoi(getenv("HOS_WGRAD_NARROW_MAX")) : 256;
-            return a.N > narrow_max ? launch3<256, MODE_WGRAD, __bf16>(a, splits, stream) : launch3<128, MODE_WGRAD, __bf16>(a, splits, stream);
+            return a.N > 256 ? launch3<256, MODE_WGRAD, __bf16>(a, splits, stream) : launch3<128, MODE_WGRAD, __bf16>(a, splits, stream);
         }
     }
 }

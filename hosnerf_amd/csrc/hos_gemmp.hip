@@ -30,27 +30,11 @@
 // Epilogue: plane outputs go through a wave-private LDS staging buffer so that every global store instruction
 // writes whole 128-byte lines (the MFMA C layout gives a lane one column of 16 rows).
 #include "hos_gemm_common.h"
-#include <cstdlib>
 
-// compile-time ablation switches for timing experiments (a run-time test inside the K loop splits the basic block and
-// makes hipcc fall back to lgkmcnt(0) before every MFMA group, which serialises LDS reads and MFMAs)
-#ifndef HOS_ABLATE_MFMA
-#define HOS_ABLATE_MFMA 0
-#endif
-#ifndef HOS_ABLATE_DMA
-#define HOS_ABLATE_DMA 0
-#endif
-// Round 5, built, measured and compiled OUT by default (-DHOS_GEMMP_PERSIST=1 builds it in; scripts/build_variant.sh): PERSISTENT FWD /
-// DGRAD launches of the 256-wide tile -- one workgroup per CU walks the output tiles and the K pipeline (LDS-DMA two tiles ahead) runs
-// straight across tile boundaries, so a tile has no prologue: its first two K tiles are requested while the previous tile still
-// multiplies, and its epilogue's stores drain under the next tile's K loop.  Isolated launch at [131072,1024,1024]: 0-2 % (706 -> 691 us
-// forward, dgrad equal).  In the steps it LOSES: two-stream stage 3 31.93 vs 31.29 ms, one stream 33.03 vs 32.97, stage 1 6.42 vs 6.39,
-// the 1080p frame 3958 vs 3936-3951 ms (three / two alternations on one box, profiles/r05_persist_step_ab.txt) -- one workgroup per tile
-// lets the other stream's kernels take CUs tile by tile and lets the dispatcher balance the tail, a persistent launch holds its CUs
-// from its first tile to its last.
-#ifndef HOS_GEMMP_PERSIST
-#define HOS_GEMMP_PERSIST 0
-#endif
+// Round 5 result, kept as a record: a persistent form of the FWD / DGRAD launches (one workgroup per CU walking the output tiles, the
+// K pipeline running across tile boundaries) gained 0-2 % on an isolated [131072,1024,1024] launch and LOST in every step (two-stream
+// stage 3 31.93 vs 31.29 ms): a persistent launch holds its CUs from its first tile to its last, one workgroup per tile lets the other
+// stream's kernels take CUs tile by tile.  It was removed; profiles/r05_persist_step_ab.txt, profiles/r04_gemmp_persistent_experiment.json.
 
 namespace {
 
@@ -130,10 +114,8 @@ __device__ __forceinline__ s16x4 lds_tr(const char* p) {
 }
 
 // TR = false: both operands k-contiguous (FWD, DGRAD).  TR = true: both operands reduction-row-major (WGRAD).
-// PERSIST: the workgroup walks output tiles blockIdx.x, blockIdx.x + gridDim.x, ... (k-contiguous form, BN = 256, nk >= 2).
-template <int BN, int EPI, typename EIN, bool TR, bool PERSIST>
+template <int BN, int EPI, typename EIN, bool TR>
 __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
-    static_assert(!PERSIST || (!TR && BN == 256), "persistent form: k-contiguous operands, 256-wide tile");
     typedef typename PVec<EIN>::x8 ex8;
     constexpr int WN = 2;
     constexpr int TM = PBM / (4 * 32);       // 2
@@ -162,18 +144,17 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
         tm_i = (bid / a.tiles_n) % a.tiles_m;
         split = bid / (a.tiles_n * a.tiles_m);
     };
-    int vb = blockIdx.x;
-    decode(vb);
-    int i0 = tm_i * PBM, j0 = tn_i * BN;
-    const int kt_begin = PERSIST ? 0 : split * a.kt_per_split;
-    const int kt_end = PERSIST ? a.nk : min(a.nk, kt_begin + a.kt_per_split);
+    decode(blockIdx.x);
+    const int i0 = tm_i * PBM, j0 = tn_i * BN;
+    const int kt_begin = split * a.kt_per_split;
+    const int kt_end = min(a.nk, kt_begin + a.kt_per_split);
     if (kt_begin >= kt_end) return;
 
     // ---- DMA plan of this wave -----------------------------------------------------------------------------------
     const bool isB = wave >= 4;                  // waves 0-3 stage the A tile, waves 4-7 the B tile
     const int quarter = wave & 3;                // ... one quarter of it each
     const int nq = isB ? QB : QA;                // instructions per K tile
-    int g_row0 = isB ? j0 : i0;                  // first output row (k-contiguous) / first column (TR) of this side
+    const int g_row0 = isB ? j0 : i0;            // first output row (k-contiguous) / first column (TR) of this side
     const int g_limit = isB ? a.N : a.M;
     // Source arrays selected ONCE into scalars.  (Selecting them inside the DMA lambda made hipcc build a pointer
     // table in scratch; every scratch_load result was then waited for with vmcnt(0), which drained the LDS-DMA
@@ -192,7 +173,7 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
     // TR form: instruction q covers 1 KB of this wave's 8 reduction rows; pitch = 4 * (columns of the tile)
     const int tr_pitch = isB ? B_PITCH : A_PITCH;
 
-    auto issue_dma = [&](int q, int kt, int stage, int row0) {
+    auto issue_dma = [&](int q, int kt, int stage) {
         size_t off;            // 64-bit: 4 Mi rows x 576 columns x 2 planes already exceeds 2^32 elements (65 536-ray proposal levels)
         const uint16_t* P;
         if constexpr (!TR) {
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
             P = seg1 ? P1 : P0;
             const int ld = seg1 ? ld1 : ld0;
             const int kb = seg1 ? kt - kt0 : kt;                         // 32-column block of the row
-            int gr = row0 + kc_row + 8 * q;
+            int gr = g_row0 + kc_row + 8 * q;
             gr = gr < g_limit ? gr : g_limit - 1;                       // clamp: out-of-range rows are never stored
             const int chunk = kc_pos ^ (kc_swz | ((q & 1) << 2));       // 0-3: hi k 0..31, 4-7: lo
             off = (size_t)gr * (size_t)(2 * ld) + (size_t)(kb * 64 + chunk * 8);
@@ -210,7 +191,7 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
             const int m = quarter * 8 + pos / tr_pitch;                 // reduction row inside the K tile
             const int rb = pos % tr_pitch;                              // byte inside the LDS row
             const int unit = (rb >> 6) ^ (m & 3);                       // source 64-byte unit (swizzle on the source)
-            int gc = row0 + (unit >> 1) * 32 + ((rb >> 4) & 3) * 8;     // logical column of this 16-byte piece
+            int gc = g_row0 + (unit >> 1) * 32 + ((rb >> 4) & 3) * 8;     // logical column of this 16-byte piece
             gc = gc < ((g_limit + 7) & ~7) ? gc : 0;                    // clamp: columns past the operand are never stored
             off = (size_t)(kt * PBK + m) * (size_t)(2 * ld0) + (size_t)((gc >> 5) * 64 + (unit & 1) * 32 + (gc & 31));
         }
@@ -218,7 +199,7 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
     };
 
     f32x16 acc[TM][TN];
-    unsigned bw_ok_mask = 0xffffffffu;         // DGRAD: blocks whose ReLU bit dword exists (set per tile)
+    unsigned bw_ok_mask = 0xffffffffu;         // DGRAD: blocks whose ReLU bit dword exists
     const int l31 = lane & 31, lhi = lane >> 5;
     float dbsum[TM];
 #pragma unroll
@@ -333,54 +314,18 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
     // instead of together with the A wave in the last group, where both stalled on DMA issue at once (-3 %).
     // All waits are explicit (asm s_waitcnt + raw s_barrier): __syncthreads() would drain the LDS-DMA queue
     // (vmcnt(0)) wherever the compiler places it, which serialises DMA and MFMA at one workgroup per CU.
-    auto issue_tile = [&](int kt, int stage, int row0) {
-        if (HOS_ABLATE_DMA) return;
+    auto issue_tile = [&](int kt, int stage) {
 #pragma unroll
-        for (int q = 0; q < QMAX; ++q) if (q < nq) issue_dma(q, kt, stage, row0);
+        for (int q = 0; q < QMAX; ++q) if (q < nq) issue_dma(q, kt, stage);
     };
 
-#ifdef HOS_TRACE   // block timeline: entry / loop start / loop end / exit of workgroups 0 and 300 (second round)
-// (slots 0 and 3 also record the constant 100 MHz counter: shader cycles / wall time = the effective clock of the launch)
-#define HOS_BSTAMP(slot) do { if ((blockIdx.x == 0 || blockIdx.x == 300) && lane == 0 && a.f32.aux) { \
-        reinterpret_cast<long long*>(a.f32.aux)[256 + ((blockIdx.x ? 1 : 0) * 8 + wave) * 4 + (slot)] = clock64(); \
-        if ((slot) == 0 || (slot) == 3) reinterpret_cast<long long*>(a.f32.aux)[320 + ((blockIdx.x ? 1 : 0) * 8 + wave) * 2 + ((slot) ? 1 : 0)] = wall_clock64(); } } while (0)
-#else
-#define HOS_BSTAMP(slot) do {} while (0)
-#endif
-#ifdef HOS_TRACE2  // per-tile timeline of workgroups 0 and 100, waves 0 and 4: K loop start / end, epilogue end, next tile ready
-    int tile_no = 0;
-#define HOS_TSTAMP(slot) do { if ((blockIdx.x == 0 || blockIdx.x == 100) && lane == 0 && (wave & 3) == 0 && a.f32.aux && tile_no < 16) \
-        reinterpret_cast<long long*>(a.f32.aux)[(((blockIdx.x ? 1 : 0) * 2 + (wave >> 2)) * 16 + tile_no) * 4 + (slot)] = clock64(); } while (0)
-#define HOS_WSTAMP(slot) do { if ((blockIdx.x == 0 || blockIdx.x == 100) && lane == 0 && (wave & 3) == 0 && a.f32.aux) { \
-        reinterpret_cast<long long*>(a.f32.aux)[256 + (((blockIdx.x ? 1 : 0) * 2 + (wave >> 2)) * 2 + (slot)) * 2] = wall_clock64(); \
-        reinterpret_cast<long long*>(a.f32.aux)[256 + (((blockIdx.x ? 1 : 0) * 2 + (wave >> 2)) * 2 + (slot)) * 2 + 1] = clock64(); } } while (0)
-// every workgroup: wall clock at entry / exit and its XCC id (aux[512 + 4 b ..])
-#define HOS_ASTAMP(slot) do { if (lane == 0 && wave == 0 && a.f32.aux && blockIdx.x < 4096) { \
-        reinterpret_cast<long long*>(a.f32.aux)[512 + 4 * blockIdx.x + (slot)] = wall_clock64(); \
-        if ((slot) == 0) { unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); \
-                           unsigned hwid; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid)); \
-                           reinterpret_cast<long long*>(a.f32.aux)[512 + 4 * blockIdx.x + 2] = (long long)(xcc & 0xf) | ((long long)hwid << 8); } } } while (0)
-#else
-#define HOS_TSTAMP(slot) do {} while (0)
-#define HOS_WSTAMP(slot) do {} while (0)
-#define HOS_ASTAMP(slot) do {} while (0)
-#endif
-    HOS_BSTAMP(0);
-    HOS_WSTAMP(0);
-    HOS_ASTAMP(0);
-    issue_tile(kt_begin, 0, g_row0);
-    if (kt_begin + 1 < kt_end) issue_tile(kt_begin + 1, 1, g_row0);
+    issue_tile(kt_begin, 0);
+    if (kt_begin + 1 < kt_end) issue_tile(kt_begin + 1, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
     HOS_READ_A(a0h, a0l, 0u, 0);
     HOS_READ_B(b0h, b0l, 0u, 0, 0);
 
-#ifdef HOS_TRACE   // timing experiment: lane 0 of every wave of workgroup 0 stamps the phase boundaries of K tiles 8..11
-    long long* const trbuf = reinterpret_cast<long long*>(a.f32.aux);
-#define HOS_STAMP(slot) do { if (blockIdx.x == 0 && first_tile && lane == 0 && trbuf && kt >= kt_begin + 8 && kt < kt_begin + 12) trbuf[(wave * 4 + (kt - kt_begin - 8)) * 8 + (slot)] = clock64(); } while (0)
-#else
-#define HOS_STAMP(slot) do {} while (0)
-#endif
     // One quarter = NM MFMAs (3 products x TM x TH tiles) with the LDS reads of the NEXT quarter (and the DMA requests of a
     // later tile) issued BETWEEN them: `fill(i)` runs right behind MFMA i.  A wave issues
     // in order, so anything placed in front of an MFMA group delays it; placed between MFMAs it costs nothing
@@ -399,11 +344,9 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
         __builtin_amdgcn_s_setprio(1);                                                                    \
         _Pragma("unroll") for (int i = 0; i < NM; ++i) {                                                  \
             HOS_ORDER_DECODE(i);                                                                          \
-            if (!HOS_ABLATE_MFMA) {                                                                       \
-                if (pr == 0)      acc[x][(YH) * TH + y] = pmfma(AL[x].v, BH[y].v, acc[x][(YH) * TH + y]); \
-                else if (pr == 1) acc[x][(YH) * TH + y] = pmfma(AH[x].v, BL[y].v, acc[x][(YH) * TH + y]); \
-                else              acc[x][(YH) * TH + y] = pmfma(AH[x].v, BH[y].v, acc[x][(YH) * TH + y]); \
-            }                                                                                             \
+            if (pr == 0)      acc[x][(YH) * TH + y] = pmfma(AL[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
+            else if (pr == 1) acc[x][(YH) * TH + y] = pmfma(AH[x].v, BL[y].v, acc[x][(YH) * TH + y]);     \
+            else              acc[x][(YH) * TH + y] = pmfma(AH[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
             __builtin_amdgcn_sched_barrier(0);                                                            \
             FILL(i);                                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                            \
@@ -412,14 +355,6 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
     } while (0)
 
     unsigned so = 0;                     // byte offset of the stage holding the K tile being multiplied
-    bool first_tile = true;
-    HOS_BSTAMP(1);
-  for (;;) {                             // ---- output tiles of this workgroup (one unless PERSIST) ----
-    // the tile behind this one: its first K tiles are requested by the last two iterations of this tile's loop
-    const int vnext = vb + (int)gridDim.x;
-    const bool has_next = PERSIST && vnext < nb;
-    int n_row0 = 0;
-    if (has_next) { decode(vnext); n_row0 = isB ? tn_i * BN : tm_i * PBM; }
 #pragma unroll
     for (int x = 0; x < TM; ++x)
 #pragma unroll
@@ -433,7 +368,6 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
     // asm waits and assumes the LDS-DMA writes may alias), which drains the DMA queue once per K tile.
     float bias_r[TN];
     uint32_t bw[TM][TN / 2];
-    bw_ok_mask = 0xffffffffu;
     if constexpr (EPI == PEPI_PLANES_FWD) {
         const float* const bp = a.bias != nullptr ? a.bias : reinterpret_cast<const float*>(a.B);
         const int nmax = a.bias != nullptr ? a.N - 1 : 0;
@@ -457,38 +391,28 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
                 if (!ok) bw_ok_mask &= ~(1u << (x * (TN / 2) + yp));
             }
     }
-    HOS_TSTAMP(0);
     for (int kt = kt_begin; kt < kt_end; ++kt) {
         const unsigned sn = STAGE - so;
         const bool more1 = kt + 1 < kt_end;
         const int dstage = so ? 1 : 0;
-        // K tile v+1 / v+2 of this workgroup's stream: inside this output tile, or the first / second of the next one
-        // (the one-tile form keeps kt + 1 / kt + 2 as plain induction values: with the selects below in the address arithmetic
-        // of every request the WGRAD launch was 5 % slower, 669 -> 706 us at [1024,1024,131072], same box)
-        bool dma1, dma2; int kt1, row1, kt2, row2;
-        if constexpr (PERSIST) {
-            const bool w1 = kt + 1 >= kt_end, w2 = kt + 2 >= kt_end;
-            dma1 = !w1 || has_next; dma2 = !w2 || has_next;
-            kt1 = w1 ? kt + 1 - kt_end : kt + 1; row1 = w1 ? n_row0 : g_row0;
-            kt2 = w2 ? kt + 2 - kt_end : kt + 2; row2 = w2 ? n_row0 : g_row0;
-        } else {
-            dma1 = kt + 1 < kt_end; dma2 = kt + 2 < kt_end;
-            kt1 = kt + 1; kt2 = kt + 2; row1 = row2 = g_row0;
-        }
-        const bool b_issue = !HOS_ABLATE_DMA && isB && dma1 && (PERSIST ? !(first_tile && kt == kt_begin) : kt > kt_begin);     // (the prologue requested tile 1)
-        const bool a_issue = !HOS_ABLATE_DMA && !isB && dma2;
-        HOS_STAMP(0);
+        // (kt1 / kt2 are plain induction values held in named locals.  With selects in the address arithmetic of every request
+        // the WGRAD launch was 5 % slower, 669 -> 706 us at [1024,1024,131072], same box; with `kt + 1` written inside the fill
+        // lambdas, which capture the loop variable by reference, hipcc recomputes every request's 64-bit row offset inside the K
+        // loop of the 256-wide tile: 30 more VALU instructions per K tile)
+        const bool dma1 = kt + 1 < kt_end, dma2 = kt + 2 < kt_end;
+        const int kt1 = kt + 1, kt2 = kt + 2;
+        const bool b_issue = isB && dma1 && kt > kt_begin;       // (the prologue requested tile 1)
+        const bool a_issue = !isB && dma2;
         auto fill1 = [&](int i) {                // under (A0,B0): B1 = (s0, yh1); B waves: the DMA of tile v+1
             if (i == 1) HOS_READ_B1(b1h, b1l, so, 0, 1, 0);
             if (i == 3) HOS_READ_B1(b1h, b1l, so, 0, 1, 1);
             constexpr int D0 = NM / 3, ND = NM - D0;          // DMA slots: the last two thirds of the group
             if (b_issue && i >= D0) {
 #pragma unroll
-                for (int q = (i - D0) * QMAX / ND; q < (i - D0 + 1) * QMAX / ND; ++q) if (q < nq) issue_dma(q, kt1, dstage ^ 1, row1);
+                for (int q = (i - D0) * QMAX / ND; q < (i - D0 + 1) * QMAX / ND; ++q) if (q < nq) issue_dma(q, kt1, dstage ^ 1);
             }
         };
         HOS_GROUP(a0h, a0l, b0h, b0l, 0, fill1);
-        HOS_STAMP(1);
         auto fill2 = [&](int i) {                // under (A0,B1): A1 = (s1), B0 = (s1, yh0)
             if (i == 0) HOS_READ_A1(a1h, a1l, so, 1, 0);
             if (i == 1) HOS_READ_A1(a1h, a1l, so, 1, 1);
@@ -496,19 +420,15 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
             if (i == 3) HOS_READ_B1(b0h, b0l, so, 1, 0, 1);
         };
         HOS_GROUP(a0h, a0l, b1h, b1l, 1, fill2);
-        HOS_STAMP(2);
         auto fill3 = [&](int i) {                // under (A1,B0): B1 = (s1, yh1)
             if (i == 1) HOS_READ_B1(b1h, b1l, so, 1, 1, 0);
             if (i == 3) HOS_READ_B1(b1h, b1l, so, 1, 1, 1);
         };
         HOS_GROUP(a1h, a1l, b0h, b0l, 0, fill3);
-        HOS_STAMP(3);
         // this wave's share of tile v+1 has landed and its reads of this stage are complete; after the barrier
         // that holds for every wave, so the stage may be refilled and the other one read
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        HOS_STAMP(4);
         asm volatile("s_barrier" ::: "memory");
-        HOS_STAMP(5);
         auto fill4 = [&](int i) {                // under (A1,B1): A0, B0 of tile kt+1, A waves: the DMA of tile v+2
             if (more1) {
                 if (i == 0) HOS_READ_A1(a0h, a0l, sn, 0, 0);
@@ -519,18 +439,13 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
             constexpr int D0 = NM / 3, ND = NM - D0;
             if (a_issue && i >= D0) {
 #pragma unroll
-                for (int q = (i - D0) * QMAX / ND; q < (i - D0 + 1) * QMAX / ND; ++q) if (q < nq) issue_dma(q, kt2, dstage, row2);
+                for (int q = (i - D0) * QMAX / ND; q < (i - D0 + 1) * QMAX / ND; ++q) if (q < nq) issue_dma(q, kt2, dstage);
             }
         };
         HOS_GROUP(a1h, a1l, b1h, b1l, 1, fill4);
-        HOS_STAMP(7);
         so = sn;
     }
-    HOS_BSTAMP(2);
-    HOS_TSTAMP(1);
-    // Here: every wave has passed the last iteration's barrier, so nobody reads the stage of the last K tile any more
-    // (`STAGE - so`).  PERSIST: the A waves' requests for the next tile's second K tile are in flight into the A half of that
-    // stage, the next tile's first K tile has landed in stage `so`; the B half of the free stage is the epilogue's staging memory.
+    // Here: every wave has passed the last iteration's barrier, so nobody reads the stage of the last K tile any more.
 
     // ---------------------------------------------------------------------------------------- epilogues
     if constexpr (EPI == PEPI_F32 || EPI == PEPI_WGRAD) {
@@ -574,8 +489,8 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
         // column 32 yy + (lane&31)) of the block), and DGRAD, whose accumulators have the same layout, reads its own dword
         // back: 8 KB per tile instead of the 256 KB of the fp16 planes of the layer input (whose fetch at ~11 B/clk/CU
         // cost ~16 us at the end of every tile: 110 us of an 817 us launch at M = 131072).
-        constexpr int YB = PERSIST ? 1 : 2;                       // 32-column blocks per staging round (4 / 8 KB per wave)
-        if constexpr (!PERSIST) asm volatile("s_barrier" ::: "memory");       // all waves are done with the stage memory
+        constexpr int YB = 2;                                     // 32-column blocks per staging round (8 KB per wave)
+        asm volatile("s_barrier" ::: "memory");                   // all waves are done with the stage memory
         // the loads issued at the top of the tile have landed (the K loop waited vmcnt(0)); make that visible to the compiler
         if constexpr (EPI == PEPI_PLANES_FWD) {
 #pragma unroll
@@ -588,14 +503,13 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
                 for (int yp = 0; yp < TN / 2; ++yp) asm volatile("" : "+v"(bw[x][yp]));
         }
         // staging memory as raw LDS addresses; every access below is an asm statement (see the note at the top of the tile)
-        const unsigned stg = lds_base + (PERSIST ? (STAGE - so) + A_TILE + wave * 4096 : wave * 8192);
+        const unsigned stg = lds_base + wave * 8192;
         const unsigned stg_w = stg + (4 * lhi * (32 * YB) + l31) * 4;                    // + row / block immediates
-        const unsigned stg_r = YB == 2 ? stg + (lane >> 4) * 256 + ((lane >> 3) & 1) * 128 + (lane & 3) * 32
-                                       : stg + (lane >> 3) * 128 + (lane & 3) * 32;       // + pass * 1024
+        const unsigned stg_r = stg + (lane >> 4) * 256 + ((lane >> 3) & 1) * 128 + (lane & 3) * 32;       // + pass * 1024
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const bool dual = (EPI == PEPI_PLANES_FWD) && a.Yb != nullptr;
         const bool first = a.Y != nullptr;
-        const bool legacy_mask = (EPI == PEPI_PLANES_DGRAD) && a.bits == nullptr && a.mask != nullptr;     // never on a persistent launch
+        const bool legacy_mask = (EPI == PEPI_PLANES_DGRAD) && a.bits == nullptr && a.mask != nullptr;
         float vmax = 0.f;          // largest hidden activation: beyond the exact fp16 hi/lo range (HOS_RANGE_LIMIT)?
 #pragma unroll
         for (int x = 0; x < TM; ++x)
@@ -666,12 +580,12 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const int idx = (p0 + k) * 64 + lane;
-                                const int rl = YB == 2 ? idx >> 4 : idx >> 3, cb = YB == 2 ? (idx >> 3) & 1 : 0, half = (idx >> 2) & 1, c8 = (idx & 3) * 8;
+                                const int rl = idx >> 4, cb = (idx >> 3) & 1, half = (idx >> 2) & 1, c8 = (idx & 3) * 8;
                                 const int row = row0 + rl, col = col0 + (y0 + cb) * 32;
                                 const uint32_t sel = half ? 0x07060302u : 0x05040100u;
                                 uint4 o4 = make_uint4(__builtin_amdgcn_perm(w0[k].y, w0[k].x, sel), __builtin_amdgcn_perm(w0[k].w, w0[k].z, sel),
                                                       __builtin_amdgcn_perm(w1[k].y, w1[k].x, sel), __builtin_amdgcn_perm(w1[k].w, w1[k].z, sel));
-                                if constexpr (EPI == PEPI_PLANES_DGRAD && !PERSIST) {
+                                if constexpr (EPI == PEPI_PLANES_DGRAD) {
                                     if (legacy_mask && row < a.M && col < a.ldmask) {
                                         const uint4 mk = *reinterpret_cast<const uint4*>(a.mask + (size_t)row * (2 * a.ldmask) + (col >> 5) * 64 + c8);
                                         const uint32_t mw[4] = {mk.x, mk.y, mk.z, mk.w};
@@ -701,38 +615,8 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    HOS_TSTAMP(2);
-    if (!has_next) break;
-    // ---- next output tile: its first K tile is in stage `so`; the staging memory becomes a DMA target again ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");
-    HOS_READ_A(a0h, a0l, so, 0);
-    HOS_READ_B(b0h, b0l, so, 0, 0);
-    vb = vnext;
-    i0 = tm_i * PBM; j0 = tn_i * BN;           // (decode(vnext) above left the next tile's coordinates in tm_i / tn_i)
-    g_row0 = n_row0;
-    first_tile = false;
-    HOS_TSTAMP(3);
-#ifdef HOS_TRACE2
-    ++tile_no;
-#endif
-  }
-#ifdef HOS_TRACE2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    HOS_WSTAMP(1);
-    HOS_ASTAMP(1);
-#ifdef HOS_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    HOS_BSTAMP(3);
-#undef HOS_BSTAMP
-#undef HOS_TSTAMP
-#undef HOS_WSTAMP
-#undef HOS_ASTAMP
 #undef HOS_GROUP
 #undef HOS_ORDER_DECODE
-#undef HOS_STAMP
 #undef HOS_READ_A
 #undef HOS_READ_A1
 #undef HOS_READ_B
@@ -741,28 +625,17 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
 #undef HOS_RDTR
 }
 
-// number of compute units (persistent grids), queried once
-inline int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
-template <int BN, int EPI, typename EIN, bool TR, bool PERSIST>
+template <int BN, int EPI, typename EIN, bool TR>
 int launchp_impl(PArgs& a, int grid, hipStream_t stream) {
     constexpr size_t smem = 2 * (PBM + BN) * 128;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemmp_kernel<BN, EPI, EIN, TR, PERSIST>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemmp_kernel<BN, EPI, EIN, TR>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    hipLaunchKernelGGL((gemmp_kernel<BN, EPI, EIN, TR, PERSIST>), dim3(grid), dim3(PNT), smem, stream, a);
+    hipLaunchKernelGGL((gemmp_kernel<BN, EPI, EIN, TR>), dim3(grid), dim3(PNT), smem, stream, a);
     return hos_launch_status();
 }
 
@@ -778,13 +651,7 @@ int launchp(PArgs& a, int splits, hipStream_t stream) {
         a.kt_per_split = a.nk;
     }
     a.total = a.tiles_m * a.tiles_n * splits;
-    if constexpr (!TR && BN == 256 && HOS_GEMMP_PERSIST && (EPI == PEPI_PLANES_FWD || EPI == PEPI_PLANES_DGRAD)) {
-        static const int env_persist = getenv("HOS_GEMMP_PERSIST") ? atoi(getenv("HOS_GEMMP_PERSIST")) : 1;      // (only in a -DHOS_GEMMP_PERSIST=1 build)
-        const int cus = cu_count();
-        const bool legacy_mask = EPI == PEPI_PLANES_DGRAD && a.bits == nullptr && a.mask != nullptr;
-        if (env_persist && a.nk >= 2 && a.total > cus && !legacy_mask) return launchp_impl<BN, EPI, EIN, TR, true>(a, cus, stream);
-    }
-    return launchp_impl<BN, EPI, EIN, TR, false>(a, a.total, stream);
+    return launchp_impl<BN, EPI, EIN, TR>(a, a.total, stream);
 }
 
 // element offset of (row r, column c) in an interleaved-planes array with `ld` logical columns: hi there, lo 32 further
@@ -914,8 +781,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 
 // split-K factor of the weight gradient: one workgroup per CU, at least 8 K tiles per split
 inline int wgrad_splits(int tiles, int nk, int requested) {
-    static const int env_splits = getenv("HOS_WGRAD_SPLITS") ? atoi(getenv("HOS_WGRAD_SPLITS")) : 0;
-    int splits = env_splits > 0 ? env_splits : requested;
+    int splits = requested;
     if (splits <= 0) {
         splits = 256 / tiles > 0 ? 256 / tiles : 1;       // never more workgroups than CUs: one over costs a whole second round
         if (splits > nk / 8) splits = nk / 8 > 0 ? nk / 8 : 1;
@@ -1079,8 +945,7 @@ extern "C" int hos_linearp_wgrad(const void* dZ, int lddz, const void* X, int ld
     a.f32.C = dW; a.f32.ldc = ldw; a.f32.M = N; a.f32.N = K; a.f32.db = db;
     // 256 x 128 tiles up to K = 256: a [256,256] gradient then has two tiles x 128 splits instead of one x 256 --
     // half the atomic traffic at the same parallelism (98 -> 55 us at M = 65536)
-    static const int narrow_max = getenv("HOS_WGRAD_NARROW_MAX") ? atoi(getenv("HOS_WGRAD_NARROW_MAX")) : 256;
-    const bool wide = K > narrow_max;
+    const bool wide = K > 256;
     const int tiles = hos_cdiv(N, PBM) * hos_cdiv(K, wide ? 256 : 128);
     splits = wgrad_splits(tiles, a.nk, splits);
     // slab reduction instead of atomics when the caller lent a large enough, 16-byte aligned workspace

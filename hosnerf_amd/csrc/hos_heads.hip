@@ -9,7 +9,6 @@
 // stage-3 step = 4.4 TB/s; the first version -- a row shared by a few lanes, one 128-byte line per lane and step -- ran at 127 us
 // and was removed in round 5).  E = _Float16 (proposal MLPs) or __bf16 (the NeRF MLP's bf16-only forward, round 5).
 #include "hos_common.h"
-#include <cstdlib>
 
 namespace {
 

@@ -12,15 +12,11 @@
 // point = 12 B in (o,d,near,far amortised) + 32 B out (z, pts, x_skel, mask) + 26*8*4 B of L2 gathers.
 #include "hos_common.h"
 
-#include <cstdlib>
 // workgroups of the persistent backward kernels (they keep per-block partial sums in LDS and flush them once).  768 = three 256-thread
 // workgroups per CU: these kernels are gather-bound (26 x 8 taps per point out of L2) and one wave per SIMD hides little of that
 // latency.  Round 5, step level, three alternations on one box (profiles/r05_persist_grid_sweep.txt): stage 2 8.13-8.18 ms at 256,
 // 8.02-8.05 at 384, 7.99-8.03 at 512, 7.99-8.00 at 768; stage 3 31.33-31.36 -> 31.29-31.31; 512-ray step equal.
-static inline long persist_grid() {
-    static const long g = getenv("HOS_PERSIST_GRID") ? atol(getenv("HOS_PERSIST_GRID")) : 768;
-    return g > 0 ? g : 768;
-}
+constexpr long persist_grid = 768;
 
 namespace {
 
@@ -436,11 +432,7 @@ __device__ __forceinline__ float trilinear_zero_grad(const float* __restrict__ v
             }
             if (lane >= off) flag |= f_up;
         }
-#ifdef HOS_EXP_NO_SCATTER      // timing experiment: everything but the atomics (results invalid)
-        if (false) {
-#else
         if (act && tail) {
-#endif
 #pragma unroll
             for (int dz = 0; dz < 2; ++dz)
 #pragma unroll
@@ -842,41 +834,9 @@ __global__ __launch_bounds__(256) void lbs_forward_bwd_kernel(
 
 // g_x[p, ax] (+)= [identity] + sum_j w_j 2^j (cos(2^j x) dS_j - sin(2^j x) dC_j), features gathered from up to
 // two gradient matrices (first-layer input gradient and skip-concat gradient).
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ x, const float* __restrict__ band_w, int F,
-                                                        int identity, const float* __restrict__ dA, int lda, int colA,
-                                                        const float* __restrict__ dB, int ldb, int colB, long P,
-                                                        float* __restrict__ g_x, int accumulate, const int* __restrict__ p_dev,
-                                                        const float* __restrict__ res) {
-    const long P_full = P;
-    if (p_dev) P = min(P, (long)*p_dev);
-    const long total = P * 3;
-    if (res != nullptr)
-        for (long it = total + (long)blockIdx.x * blockDim.x + threadIdx.x; it < P_full * 3; it += (long)gridDim.x * blockDim.x) g_x[it] = res[it];
-    for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
-        const long p = it / 3;
-        const int ax = (int)(it % 3);
-        const float xv = x[it];
-        auto feat = [&](int c) {
-            float v = dA[p * lda + colA + c];
-            if (dB) v += dB[p * ldb + colB + c];
-            return v;
-        };
-        float g = 0.f;
-        int base = 0;
-        if (identity) { g += feat(ax); base = 3; }
-        for (int j = 0; j < F; ++j) {
-            const float fr = (float)(1 << j);
-            const float a = xv * fr;
-            const float wj = band_w ? band_w[j] : 1.f;
-            g += wj * fr * (cosf(a) * feat(base + j * 6 + ax) - sinf(a) * feat(base + j * 6 + 3 + ax));
-        }
-        g_x[it] = res != nullptr ? res[it] + g : (accumulate ? g_x[it] + g : g);
-    }
-}
-
 // Tiled form: a workgroup stages the feature gradients of 64 rows (dA + dB, 3 + 6F columns each) in LDS with coalesced
 // reads -- consecutive lanes read consecutive columns of a row -- and thread (row, axis) then walks ITS features in LDS.
-// The per-element kernel above has every lane of a wave reading another row (21 rows x 12 B per load instruction).
+// (A per-element kernel has every lane of a wave reading another row: 21 rows x 12 B per load instruction.)
 __global__ __launch_bounds__(256) void embed_bwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ band_w, int F,
                                                               int identity, const float* __restrict__ dA, int lda, int colA,
                                                               const float* __restrict__ dB, int ldb, int colB, long P,
@@ -985,7 +945,7 @@ extern "C" int hos_human_sample_warp_bwd(const float* pts, const float* R, const
     if (K <= 0 || K > KMAX || V < 2) return HOS_E_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long sw_chunks = (P + 255) / 256;
-    const dim3 grid((unsigned)(sw_chunks < persist_grid() ? sw_chunks : persist_grid()));
+    const dim3 grid((unsigned)(sw_chunks < persist_grid ? sw_chunks : persist_grid));
     // with a scratch [P,2] and a volume that fits LDS the scatter runs as its own bone-per-workgroup pass
     const size_t vol_bytes = (size_t)V * V * V * sizeof(float);
     const bool split = scratch != nullptr && vol_bytes <= 128 * 1024 && P >= 8192;
@@ -1015,7 +975,7 @@ extern "C" int hos_lbs_forward_bwd(const float* cnl_pts, const float* R_fwd, con
         return HOS_E_ARG;
     if (K <= 0 || K > KMAX || CL < K || (CL & 3) || V < 2) return HOS_E_SHAPE;
     const long lb_chunks = (P + 255) / 256;
-    hipLaunchKernelGGL(lbs_forward_bwd_kernel, dim3((unsigned)(lb_chunks < persist_grid() ? lb_chunks : persist_grid())), dim3(256), 0,
+    hipLaunchKernelGGL(lbs_forward_bwd_kernel, dim3((unsigned)(lb_chunks < persist_grid ? lb_chunks : persist_grid)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), cnl_pts, R_fwd, T_fwd, vol_cl, V, CL, bbox_min, bbox_scale,
                        (long)P, K, g_x_deform, g_cnl, g_vol_cl, g_R, g_T, rows_dev);
     return hos_launch_status();
@@ -1045,15 +1005,9 @@ static int embed_bwd_launch(const float* x, const float* band_w, int num_freqs, 
                             const int32_t* rows_dev, const float* res, hos_stream_t stream) {
     if (!x || !dA || !g_x || P <= 0) return HOS_E_ARG;
     if (num_freqs < 1 || num_freqs > 16) return HOS_E_SHAPE;
-    static const bool tiled = !(getenv("HOS_EMBED_BWD_TILED") && atoi(getenv("HOS_EMBED_BWD_TILED")) == 0);
-    if (tiled) {
-        const long b = (P + 63) / 64;
-        hipLaunchKernelGGL(embed_bwd_tiled_kernel, dim3((unsigned)(b > 8192 ? 8192 : b)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                           band_w, num_freqs, identity, dA, lda, colA, dB, ldb, colB, (long)P, g_x, accumulate, rows_dev, res);
-        return hos_launch_status();
-    }
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(grid_for(P * 3)), dim3(256), 0, static_cast<hipStream_t>(stream), x, band_w,
-                       num_freqs, identity, dA, lda, colA, dB, ldb, colB, (long)P, g_x, accumulate, rows_dev, res);
+    const long b = (P + 63) / 64;
+    hipLaunchKernelGGL(embed_bwd_tiled_kernel, dim3((unsigned)(b > 8192 ? 8192 : b)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                       band_w, num_freqs, identity, dA, lda, colA, dB, ldb, colB, (long)P, g_x, accumulate, rows_dev, res);
     return hos_launch_status();
 }
 

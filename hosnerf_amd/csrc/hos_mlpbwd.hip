@@ -14,7 +14,6 @@
 //   roofline: HBM.  12 B x M x 128 per launch; MFMA time is ~1/3 of the memory time at 11 B/clk/CU.
 // Reference: the autograd backward of nn.Linear + ReLU in core/nets/human_nerf/non_rigid_motion_mlps/mlp_offset.py:54-70.
 #include "hos_gemm_common.h"
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -135,14 +134,6 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int tr_g = lane >> 4, tr_p = lane & 15;
-#ifdef HOS_MB_TRACE   // timing experiment: phase stamps of workgroups 0 and 200 in the (otherwise unused) workspace
-    long long* const trb = reinterpret_cast<long long*>(a.ws);
-    int trn = 0;
-#define MB_STAMP() do { if ((blockIdx.x == 0 || blockIdx.x == 200) && t == 0 && trn < 60) trb[(blockIdx.x ? 64 : 0) + trn++] = clock64(); } while (0)
-#else
-#define MB_STAMP() do {} while (0)
-#endif
-    MB_STAMP();
     const int tr_row = 8 * (tr_g >> 1) + (tr_p >> 2);               // reduction row inside a 16-row step
     const int tr_col = 16 * (tr_g & 1) + 4 * (tr_p & 3);            // column inside a 32-column tile
 
@@ -254,18 +245,13 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
             *reinterpret_cast<bf16x4*>(Wl + row * PW + c4 * 8) = l;
         }
     }
-    MB_STAMP();
     if constexpr (PF2) {
         while (rb < nrb) {
             sstore(rzA, rxA);
-            MB_STAMP();
             __syncthreads();                        // tile (and, the first time, W) visible
-            MB_STAMP();
             if (rb + 2 * G < nrb) gload(rzA, rxA, rb + 2 * G);
             compute(rb);
-            MB_STAMP();
             __syncthreads();                        // every wave is done with this tile before it is overwritten
-            MB_STAMP();
             rb += G;
             if (rb >= nrb) break;
             sstore(rzB, rxB);
@@ -288,13 +274,8 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
     // ---- dW: one partial [N_, K_] per workgroup.  256 workgroups adding 16 K floats each into the SAME 64 KB with fp32
     // atomics serialise in L2 (measured: 35 us of a 139 us launch); with a workspace every workgroup stores its slab with
     // plain 16-byte stores and mlp_bwd_reduce_kernel sums the slabs (8-way atomics only).
-    MB_STAMP();
     GemmArgs ew{};
-#ifdef HOS_MB_TRACE
-    if (false) {
-#else
     if (a.ws != nullptr && a.ws_dw) {
-#endif
         ew.C = a.ws + (size_t)blockIdx.x * (N_ * K_ + N_); ew.ldc = K_; ew.M = N_; ew.N = K_; ew.epi = HOS_EPI_NONE;
 #pragma unroll
         for (int j = 0; j < WPW; ++j) {
@@ -319,13 +300,11 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
             for (int k = t; k < MB_NT; k += G) { const float4 v = red[k]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
             const float sv[4] = {s.x, s.y, s.z, s.w};
             bool direct = true;
-#ifndef HOS_MB_TRACE
             if (a.ws != nullptr) {      // 256 workgroups x one atomic per bias element on the SAME address cost 10-20 us: slab tail
                 const int nk = a.ws_dw ? N_ * K_ : 0;
                 *reinterpret_cast<float4*>(a.ws + (size_t)blockIdx.x * (nk + N_) + nk + t * 4) = s;
                 direct = false;
             }
-#endif
             if (direct) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
@@ -333,11 +312,6 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
             }
         }
     }
-#ifdef HOS_MB_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MB_STAMP();
-#endif
-#undef MB_STAMP
 }
 
 // ---- WGRAD of a 256-wide layer, whole tiles only (M % 32 == 0, N == 256, K == 32 KT, slab workspace): nothing in the loop is
@@ -560,16 +534,11 @@ __global__ __launch_bounds__(256) void mlp_bwd_reduce_batch_kernel(const ReduceB
 thread_local bool g_defer = false;
 thread_local ReduceBatch g_batch = {};
 
-static inline int reduce_split() {
-    static const int v = getenv("HOS_MB_RSPLIT") ? atoi(getenv("HOS_MB_RSPLIT")) : MB_RSPLIT;
-    return v > 0 ? v : MB_RSPLIT;
-}
-
 static int flush_reduce_batch(hipStream_t stream) {
     if (g_batch.count == 0) return 0;
     const ReduceJob& L = g_batch.j[g_batch.count - 1];
     const int blocks = L.first_block + hos_cdiv(L.nk + L.n_, 1024);
-    hipLaunchKernelGGL(mlp_bwd_reduce_batch_kernel, dim3(blocks, reduce_split()), dim3(256), 0, stream, g_batch);
+    hipLaunchKernelGGL(mlp_bwd_reduce_batch_kernel, dim3(blocks, MB_RSPLIT), dim3(256), 0, stream, g_batch);
     g_batch.count = 0;
     return hos_launch_status();
 }
@@ -592,7 +561,6 @@ int launch_mb(MlpBwdArgs a, size_t ws_floats, hipStream_t stream) {
     const int nk = a.ws_dw ? N_ * K_ : 0;
     if (a.ws != nullptr && (grid < 32 || ws_floats < (size_t)grid * (nk + N_) || (!a.ws_dw && a.db == nullptr))) a.ws = nullptr;
     hipLaunchKernelGGL((mlp_bwd_kernel<NT, KT, DG>), dim3(grid), dim3(MB_NT), smem, stream, a);
-#ifndef HOS_MB_TRACE
     if (a.ws != nullptr) {
         if (g_defer) {
             if (g_batch.count == MB_BATCH) { const int rc = flush_reduce_batch(stream); if (rc != 0) return rc; }
@@ -601,11 +569,10 @@ int launch_mb(MlpBwdArgs a, size_t ws_floats, hipStream_t stream) {
                           g_batch.count ? g_batch.j[g_batch.count - 1].first_block + hos_cdiv(g_batch.j[g_batch.count - 1].nk + g_batch.j[g_batch.count - 1].n_, 1024) : 0};
             ++g_batch.count;
         } else {
-            hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(nk + N_, 1024), reduce_split()), dim3(256), 0, stream,
+            hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(nk + N_, 1024), MB_RSPLIT), dim3(256), 0, stream,
                                a.ws, grid, N_, K_, nk, a.dW, a.lddw, a.db, a.N, a.K);
         }
     }
-#endif
     return hos_launch_status();
 }
 
@@ -614,10 +581,9 @@ template <int KT>
 int launch_wgrad_fast(MlpBwdArgs a, size_t ws_floats, hipStream_t stream) {
     constexpr int N_ = 256, K_ = KT * 32, R = 32, nk = N_ * K_;
     constexpr size_t smem = 2 * (size_t)R * (N_ * 2 + 32) + 2 * (size_t)R * (K_ * 2 + 32);
-    static const bool on = !(getenv("HOS_WGRAD_FAST") && atoi(getenv("HOS_WGRAD_FAST")) == 0);
     const int nrb = a.M / R;
     const int grid = nrb < 256 ? nrb : 256;
-    if (!on || a.M % R != 0 || a.N != N_ || a.K != K_ || a.m_dev != nullptr || a.ws == nullptr || grid < 32 ||
+    if (a.M % R != 0 || a.N != N_ || a.K != K_ || a.m_dev != nullptr || a.ws == nullptr || grid < 32 ||
         ws_floats < (size_t)grid * (nk + N_) || (((uintptr_t)a.ws) & 15u)) return -1;
     static bool attr_set = false;
     if (!attr_set) {
@@ -633,7 +599,7 @@ int launch_wgrad_fast(MlpBwdArgs a, size_t ws_floats, hipStream_t stream) {
                       g_batch.count ? g_batch.j[g_batch.count - 1].first_block + hos_cdiv(g_batch.j[g_batch.count - 1].nk + g_batch.j[g_batch.count - 1].n_, 1024) : 0};
         ++g_batch.count;
     } else {
-        hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(nk + N_, 1024), reduce_split()), dim3(256), 0, stream,
+        hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(nk + N_, 1024), MB_RSPLIT), dim3(256), 0, stream,
                            a.ws, grid, N_, K_, nk, a.dW, a.lddw, a.db, a.N, a.K);
     }
     return hos_launch_status();
@@ -862,15 +828,9 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                         const bf16x8 al = *reinterpret_cast<const bf16x8*>(zrow + Z_PLANE + k * 32);
                         const bf16x8 bh = tr_frag2(wfrag + k * 16 * PW, PW);
                         const bf16x8 bl = tr_frag2(wfrag + W_PLANE + k * 16 * PW, PW);
-#ifndef HOS_CB_EXP_NOMFMA
                         acc = mma3(ah, al, bh, bl, acc);
-#else
-                        acc[k & 15] += (float)ah[0] + (float)al[1] + (float)bh[2] + (float)bl[3];
-#endif
                     }
-#ifndef HOS_CB_EXP_NOW
                     loadW_part(std::integral_constant<int, SN>{}, k * RWN / NK, (k + 1) * RWN / NK);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -891,11 +851,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                                 const char* zfrag = Zh + tr_row * PZ + ((ti / KT) * 32 + tr_col) * 2;
                                 const bf16x8 ah = tr_frag2(zfrag + k * 16 * PZ, PZ);
                                 const bf16x8 al = tr_frag2(zfrag + Z_PLANE + k * 16 * PZ, PZ);
-#ifndef HOS_CB_EXP_NOMFMA
                                 accW[acc_off(s) + j] = mma3(ah, al, bh, bl, accW[acc_off(s) + j]);
-#else
-                                accW[acc_off(s) + j][k & 15] += (float)ah[0] + (float)al[1] + (float)bh[2] + (float)bl[3];
-#endif
                             }
                         }
                     }
@@ -959,9 +915,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                     }
                 }
                 sstoreX(std::integral_constant<int, s + 1 < S ? s + 1 : 0>{});
-#ifndef HOS_CB_EXP_NOW
                 storeW(std::integral_constant<int, s + 1 < S ? s + 1 : 0>{});
-#endif
                 __syncthreads();
             }
         }, std::make_integer_sequence<int, S>{});
@@ -1216,7 +1170,7 @@ extern "C" int hos_mlp_chain_bwd(int cfg, const float* dZ, int lddz, int M, cons
             ++g_batch.count;
         } else {
             const ReduceJob& J = jobs[s];
-            hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(J.nk + J.n_, 1024), reduce_split()), dim3(256), 0, st,
+            hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3(hos_cdiv(J.nk + J.n_, 1024), MB_RSPLIT), dim3(256), 0, st,
                                J.ws, J.slabs, J.n_, J.k_, J.nk, J.dW, J.lddw, J.db, J.N, J.K);
         }
     }

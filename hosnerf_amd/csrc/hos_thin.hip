@@ -14,17 +14,12 @@
 //   roofline: HBM, 8 B (FWD) / 12 B (DGRAD) per row and column.
 // Reference: CanonicalMLP.forward, core/nets/human_nerf/canonical_mlps/mlp_rgb_sigma.py:49-58, and its autograd.
 #include "hos_gemm_common.h"
-#include <cstdlib>
 #include <type_traits>
 
-#ifndef HOS_THIN_PF2_MAXKS
-#define HOS_THIN_PF2_MAXKS 16        // fast forward kernel: two tiles of register prefetch up to this many reduction steps
-#endif
-#ifndef HOS_THIN_R_FWD
-#define HOS_THIN_R_FWD 32          // rows per forward tile (64 measured 3-5 % slower once the epilogue stopped loading the bias)
-#endif
-
 namespace {
+
+constexpr int TH_PF2_MAXKS = 16;     // fast forward kernel: two tiles of register prefetch up to this many reduction steps
+constexpr int TH_R_FWD = 32;         // rows per forward tile (64 measured 3-5 % slower once the epilogue stopped loading the bias)
 
 template <typename E> struct V8 { typedef E t __attribute__((ext_vector_type(8))); typedef E q __attribute__((ext_vector_type(4))); };
 
@@ -64,14 +59,8 @@ constexpr int TH_NT = 512;
 // (slot = 2 row mod 16) makes every read a 2-way conflict.  Measured at [262144, 256, 256]: DGRAD 203 -> 201 us (164 -> 160 with
 // mask bits) with 16 B; the forward kernels were FASTER with 32 B (138 vs 149 us: they are bound by MFMA + VALU issue of the
 // SIMD's two waves, not by LDS cycles, and the staging writes of the next tile interleave differently) -- so each keeps its own.
-#ifndef HOS_THIN_PAD_DGRAD
-#define HOS_THIN_PAD_DGRAD 16
-#endif
-#ifndef HOS_THIN_PAD_FWD
-#define HOS_THIN_PAD_FWD 32
-#endif
-constexpr int TH_PAD_FWD = HOS_THIN_PAD_FWD;
-template <bool DGRAD> constexpr int th_pad() { return DGRAD ? HOS_THIN_PAD_DGRAD : HOS_THIN_PAD_FWD; }
+constexpr int TH_PAD_DGRAD = 16, TH_PAD_FWD = 32;
+template <bool DGRAD> constexpr int th_pad() { return DGRAD ? TH_PAD_DGRAD : TH_PAD_FWD; }
 constexpr int TH_MP = 264;     // LDS pitch of a mask row: 256 columns + the 16-byte group a window at an unaligned column spills into
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
     typedef typename std::conditional<DGRAD, __bf16, _Float16>::type E;
     typedef typename V8<E>::t e8;
     typedef typename V8<E>::q e4;
-    constexpr int R = DGRAD ? 32 : HOS_THIN_R_FWD;
+    constexpr int R = DGRAD ? 32 : TH_R_FWD;
     constexpr int KD = KS * 16;
     constexpr int P = KD * 2 + th_pad<DGRAD>();          // LDS row pitch of one plane (bytes), see th_pad
     constexpr int PLANE = R * P, BUF = 2 * PLANE;        // hi, lo
@@ -97,14 +86,6 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int col0 = wave * 32;                          // this wave's output columns
-#ifdef HOS_TH_TRACE   // timing experiment: phase stamps of workgroup 0 / wave 0 over the bias array (results invalid)
-    long long* const trb = reinterpret_cast<long long*>(const_cast<float*>(a.bias));
-    int trn = 0;
-#define TH_STAMP() do { if (blockIdx.x == 0 && t == 0 && trn < 120) trb[trn++] = clock64(); } while (0)
-#else
-#define TH_STAMP() do {} while (0)
-#endif
-    TH_STAMP();
 
     // ---- this wave's slice of the weight as B fragments (hi, lo), once
     e8 bh[KS], bl[KS];
@@ -216,15 +197,12 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
     const int ntiles = (a.M + R - 1) / R;
     const int G = gridDim.x;
     int tile = blockIdx.x;
-    TH_STAMP();
     if (tile < ntiles) { gload(tile); sstore(0); }
     if (tile + G < ntiles) gload(tile + G);              // registers are free again: the second tile starts travelling
     __syncthreads();
-    TH_STAMP();
     int b = 0;
     for (; tile < ntiles; tile += G, b ^= 1) {
         const bool more = tile + G < ntiles;
-        TH_STAMP();
         if constexpr (DGRAD) bits_cur = bits_staged;      // this tile's ReLU bits (staged together with its operands)
         const char* hi = buf0 + b * BUF + l31 * P + lhi * 16;
         f32x16 acc[R / 32];
@@ -243,14 +221,12 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
                 acc[rt] = mfma_e(ah, bh[s], acc[rt]);
             }
         }
-        TH_STAMP();
         // Stage the next tile BEFORE this tile's stores: vmcnt retires in order, so converting the prefetched registers
         // after the epilogue would first wait for every store just issued (a full HBM write round trip per tile).
         if (more) sstore(b ^ 1);
         // ... and the staging registers are free: the tile after next travels during this tile's stores, the barrier and the
         // whole next compute phase (a load issued at the top of an iteration had ~1 k cycles of cover, measured 10 k waiting)
         if (tile + 2 * G < ntiles) gload(tile + 2 * G);
-        TH_STAMP();
         if (col0 < a.N) {
 #pragma unroll
             for (int rt = 0; rt < R / 32; ++rt) {
@@ -297,18 +273,15 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
                 }
             }
         }
-        TH_STAMP();
         // next buffer complete; this one free for the tile after next.  (hipcc compiles __syncthreads() to `s_waitcnt
         // lgkmcnt(0); s_barrier` on this target: waves of a workgroup share the CU, so the fence does not wait for global
-        // memory operations.  What the waves wait for at this barrier is each other: HOS_TH_TRACE.)
+        // memory operations.  What the waves wait for at this barrier is each other (measured with per-phase clock stamps).)
         __syncthreads();
     }
-    TH_STAMP();
-#undef TH_STAMP
 }
 
 // ---- FWD fast path: whole tiles only (M % 32 == 0, K == 16 KS, N == 256, 16-byte aligned rows of C).
-// The generic kernel above is LATENCY-bound (HOS_TH_TRACE: per 32-row tile a wave computes for ~2.9 k cycles and waits ~4.4 k --
+// The generic kernel above is LATENCY-bound (per-phase clock stamps: per 32-row tile a wave computes for ~2.9 k cycles and waits ~4.4 k --
 // 2.0 k at the `vmcnt(0)` in front of the staging and 2.4 k at the barrier): every global load and store of its loop is
 // predicated, so the compiler has no lower bound on how many younger operations follow a prefetch and must wait for ALL of
 // them (vmcnt retires in order), i.e. also for the stores just issued and for any deeper prefetch.  One tile of loads plus one
@@ -327,7 +300,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
     constexpr int P = KD * 2 + TH_PAD_FWD;
     constexpr int PLANE = R * P, BUF = 2 * PLANE;
     constexpr int AU = R * (KD / 4) / TH_NT;             // float4 units of a tile per thread
-    constexpr bool PF2 = KS <= HOS_THIN_PF2_MAXKS;       // two tiles of register prefetch (20 steps: the registers hold weights)
+    constexpr bool PF2 = KS <= TH_PF2_MAXKS;       // two tiles of register prefetch (20 steps: the registers hold weights)
     constexpr int PFD = PF2 ? 3 : 2;
     static_assert(AU >= 1 && R * (KD / 4) % TH_NT == 0, "tile does not divide over 512 threads");
 
@@ -358,9 +331,6 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
     // this thread's float4 units of a tile: unit u = t + 512 i -> (row, 16-byte column group)
     auto gload = [&](float4 (&r)[AU], int tile) {
         tile = tile < ntiles ? tile : ntiles - 1;        // clamped, never predicated (a tile past the end is loaded, not staged)
-#ifdef HOS_EXP_SAMEA       // timing experiment: every tile is read from the workgroup's FIRST tile (cache hits; results invalid)
-        tile = blockIdx.x;
-#endif
         const float* base = a.A + (size_t)tile * R * a.lda;
 #pragma unroll
         for (int i = 0; i < AU; ++i) {
@@ -434,11 +404,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
             const float pre = (v[0] + v[1]) + (v[2] + v[3]);
             if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             big |= (fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) > HOS_RANGE_LIMIT) | (pre != pre);
-#ifdef HOS_EXP_NOSTORE     // timing experiment: results are written to the workgroup's first tile only (cache hits; results invalid)
-            *reinterpret_cast<float4*>(a.C + (size_t)(blockIdx.x * R + q4 + 4 * lhi + 8 * g) * a.ldc + colb) = make_float4(v[0], v[1], v[2], v[3]);
-#else
             *reinterpret_cast<float4*>(crow + (size_t)(8 * g) * a.ldc) = make_float4(v[0], v[1], v[2], v[3]);
-#endif
         }
         if constexpr (BITS) {
             // two lanes' 16-bit masks as ONE dword store by the even lane (same bytes in memory: bits[t] | bits[t + 1] << 16)
@@ -639,7 +605,7 @@ int launch_thin_fast(const ThinArgs& a, hipStream_t stream) {
 
 template <int KS, bool DGRAD>
 int launch_thin(const ThinArgs& a, hipStream_t stream) {
-    constexpr int R = DGRAD ? 32 : HOS_THIN_R_FWD;
+    constexpr int R = DGRAD ? 32 : TH_R_FWD;
     constexpr size_t smem = 2 * 2 * (size_t)R * (KS * 32 + th_pad<DGRAD>()) + (DGRAD ? 2 * (size_t)R * TH_MP : 0);
     static bool attr_set = false;
     if (!attr_set) {
@@ -752,9 +718,8 @@ extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int 
     // reduction steps held in registers: 4 (the folded canonical input layer, 64 columns), 8, 16, 20 (the folded skip layer:
     // [fourier 64 | h 256]; 250 VGPRs -- 24 steps for the reference-shaped 384-wide concat row do not fit two waves per SIMD)
     // whole tiles of the shapes the canonical MLP runs (256 outputs; 64 / 256 / 320 inputs): the unpredicated kernel; a ragged
-    // tail of M % 32 rows goes through the generic one (HOS_THIN_FAST=0: everything does)
-    static const bool fast_on = !(getenv("HOS_THIN_FAST") && atoi(getenv("HOS_THIN_FAST")) == 0);
-    if (fast_on && N == 256 && M >= 32 && (K == 64 || K == 256 || K == 320) && !(ldy & 3) && !((uintptr_t)Y & 15u) &&
+    // tail of M % 32 rows goes through the generic one
+    if (N == 256 && M >= 32 && (K == 64 || K == 256 || K == 320) && !(ldy & 3) && !((uintptr_t)Y & 15u) &&
         (!bias || !((uintptr_t)bias & 15u)) && !((uintptr_t)relu_bits & 3u)) {
         ThinArgs f = a;
         f.M = M & ~31;
@@ -787,8 +752,7 @@ extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     // whole tiles of a full 256 x 256 layer (or its 64-column Fourier window) with the bit mask or no mask: the unpredicated kernel;
     // ragged tail: generic
-    static const bool fast_on = !(getenv("HOS_THIN_FAST") && atoi(getenv("HOS_THIN_FAST")) == 0);
-    if (fast_on && (K == 256 || K == 64) && Npad == 256 && M >= 32 && (mask_bits || !mask) && !(lddx & 3) && !((uintptr_t)dX & 15u)) {
+    if ((K == 256 || K == 64) && Npad == 256 && M >= 32 && (mask_bits || !mask) && !(lddx & 3) && !((uintptr_t)dX & 15u)) {
         ThinArgs f = a;
         f.M = M & ~31;
         const int rc = mask_bits ? launch_thin_dgrad_fast<true>(f, s) : launch_thin_dgrad_fast<false>(f, s);

@@ -92,8 +92,6 @@ class HOSNeRF(nn.Module):
             side.wait_stream(cur)                                  # fork: everything queued so far (inputs, last step's Adam) is visible
             with torch.cuda.stream(side):
                 out = self.human(t_rand=t_rand, prologue=prologue, with_cycle=with_cycle, static_cycle=static_cycle, **batch)
-            if os.environ.get("HOS_TS_SERIAL_FWD") == "1":         # diagnostic: two streams, but the forward halves do not overlap
-                cur.wait_stream(side)
             _, hist = self.model(batch_bkg, 1.0, randomized, is_train, self.near_bkg, self.far_bkg, jitters=jitters)
             cur.wait_stream(side)                                  # join before the z-merge
             # The human outputs were allocated on the side stream and are consumed on this one (z-merge, losses, and -- as saved

@@ -595,7 +595,7 @@ class Network(FlatModule):
         h = E
         # training: every layer on the thin kernel also writes its ReLU mask as one bit per element (1 KB per 32 rows), which the
         # backward reads instead of the fp32 activations (a third of a thin dgrad launch's HBM traffic)
-        want_bits = save and ops.RELU_BITS and ops.thin_dgrad_rows(Pn)
+        want_bits = save and ops.thin_dgrad_rows(Pn)
         for i in range(8):
             L = self._cnl[i]
             Wt, bt = self._w(L)
@@ -622,11 +622,9 @@ class Network(FlatModule):
     # ------------------------------------------------------------------ HIP MLP chains (backward)
     def _nonrigid_bwd(self, specs: List[_LayerSpec], saved, x: torch.Tensor, band_w: torch.Tensor, g_xyz: torch.Tensor, rows_dev=None):
         """Parameter gradients into the flat buffer; returns d loss / d x  ([P,3]).  Every layer is 128 wide, so each
-        layer's (wgrad, dgrad) pair is one fused pass over (dZ, X) (ops.linear_bwd_fused); HOS_FUSED_BWD=0 selects the
-        two-GEMM form."""
+        layer's (wgrad, dgrad) pair is one fused pass over (dZ, X) (ops.linear_bwd_fused)."""
         E, PE, acts, fold = saved
         Pn, dev = x.shape[0], x.device
-        fused = ops.FUSED_THIN_BWD
 
         def layer_bwd(dz, X, spec, N, K, out, relu_mask, w_col0=0, bias=True, override=None):
             if override is not None:
@@ -634,11 +632,7 @@ class Network(FlatModule):
             else:
                 Wt, _ = self._w(spec)
                 gW, gb = self._w(spec, grad=True)
-            if fused:
-                ops.linear_bwd_fused(dz, X, Wt, gW, gb if bias else None, N, K, out, relu_mask, w_col0=w_col0, rows_dev=rows_dev)
-            else:
-                ops.linear_wgrad(dz, X, gW, gb if bias else None, N, K, w_col0=w_col0)
-                ops.linear_dgrad(dz, Wt, dz.shape[1], K, out, mask_src=X if relu_mask else None, w_col0=w_col0)
+            ops.linear_bwd_fused(dz, X, Wt, gW, gb if bias else None, N, K, out, relu_mask, w_col0=w_col0, rows_dev=rows_dev)
             return out
 
         dz6 = torch.empty(Pn, 32, device=dev)
@@ -647,7 +641,7 @@ class Network(FlatModule):
             # gradient buffers of the folded first layer: [128, 64] for the hann columns of W0 + [128] for the folded bias
             gfold = ops.zero_(ops.fold_grad_workspace(dev))
             gw0h, db0 = gfold[:128 * 64].view(128, 64), gfold[128 * 64:]
-        if (fold is not None and fused and ops.MLP_CHAIN_BWD and Pn >= ops.MLP_CHAIN_BWD_MIN_ROWS
+        if (fold is not None and ops.MLP_CHAIN_BWD and Pn >= ops.MLP_CHAIN_BWD_MIN_ROWS
                 and ops.get_gemm_mode() != ops.GEMM_FP32):
             # Three group launches (hos_mlpbwd.hip, chain_bwd_kernel): the gradient with respect to a layer's output stays in LDS
             # between the layers of a group; only the hand-overs (dz4, dz2), the hann-column gradients and the activations move.
@@ -906,9 +900,8 @@ class Network(FlatModule):
                 if B > chunk:
                     raise ValueError("static_cycle needs the whole ray batch in one chunk (cfg.chunk >= number of rays)")
                 sel_cnl, observe, _, count = ops.compact_rows(mask, 0.005, cnl_uses.pop(), pts)
-                # the kernels stop at `count` rows (the two-GEMM debug path of the backward, HOS_FUSED_BWD=0, has no row
-                # limit and runs over the zero-padded capacity instead)
-                ret["deform_pts_final"] = fwd_branch(sel_cnl, R_f, T_f, cond, rows_dev=count if ops.FUSED_THIN_BWD else None)
+                # the kernels stop at `count` rows
+                ret["deform_pts_final"] = fwd_branch(sel_cnl, R_f, T_f, cond, rows_dev=count)
                 ret["observe_pts"] = observe
                 ret["cycle_count"] = count
             elif with_cycle:

@@ -324,7 +324,7 @@ class MipNeRF360MLP(FlatModule):
             ops.state_embed_grad(tmp, Wt, c0, W, gb, g_embed)
 
     # ------------------------------------------------------------------ planes path (ops.GEMM_PLANES)
-    PLANES_MIN_WIDTH = int(os.environ.get("HOS_PLANES_MIN_WIDTH", "256"))
+    PLANES_MIN_WIDTH = 256
 
     def _use_planes(self) -> bool:
         return ops.get_gemm_mode() == ops.GEMM_PLANES and self.netwidth >= self.PLANES_MIN_WIDTH
@@ -333,11 +333,11 @@ class MipNeRF360MLP(FlatModule):
     # (hi, lo) forward planes: their densities steer the resampling, and 22-bit operands are what keeps `bin_idx` on the
     # reference's values; the NeRF MLP's density and colour go straight into the composite, where bf16 pairs
     # (2^-17 per product) cost ~3e-5 RGB L-inf.  Its layers then write their output once -- forward operand, ReLU
-    # mask and weight-gradient operand are the same planes -- and there is no fp16 range to guard.  HOS_NERF_BF16_FWD=0: fp16.
+    # mask and weight-gradient operand are the same planes -- and there is no fp16 range to guard.
     BF16_FWD = False
 
     def _bf16_fwd(self) -> bool:
-        return self.BF16_FWD and os.environ.get("HOS_NERF_BF16_FWD", "1") != "0"
+        return self.BF16_FWD
 
     def _weight_planes(self, need_t: bool):
         """fp16 hi/lo planes of every weight (one pass over this MLP's span of the flat buffer: the planes keep the
@@ -410,20 +410,13 @@ class MipNeRF360MLP(FlatModule):
         if self.disable_rgb:
             # Linear(width, 1) + softplus: one pass over the activation planes (a GEMM tile for one column cost 127 us per
             # 262 144 rows against 268 MB of input)
-            if ops.ROWDOT_HEADS:
-                ops.planes_rowdot(h, W, Wh[0], bt[0:1], density, p0=self.density_bias)
-            else:
-                ops.linearp_fwd(h, W, W16[-1], bt, P, 1, False, None, None, epilogue=ops.EPI_DENSITY, aux=density,
-                                p0=self.density_bias)
+            ops.planes_rowdot(h, W, Wh[0], bt[0:1], density, p0=self.density_bias)
             return density, None, (saved0,)
         bw = self.bottleneck_width
         Xv = torch.empty(P, XV_LD, device=dev)
-        if ops.ROWDOT_HEADS:         # [bottleneck 256 | density 1]: the 256 columns as ONE column tile, the density column as a row dot
-            ops.linearp_fwd(h, W, W16[-1], bt, P, bw, False, None, None, C=Xv, epilogue=ops.EPI_NONE)
-            ops.planes_rowdot(h, W, Wh[bw], bt[bw:bw + 1], density, p0=self.density_bias)
-        else:
-            ops.linearp_fwd(h, W, W16[-1], bt, P, bw + 1, False, None, None, C=Xv, epilogue=ops.EPI_NERF_HEAD,
-                            aux=density, aux_col=bw, p0=self.density_bias)
+        # [bottleneck 256 | density 1]: the 256 columns as ONE column tile, the density column as a row dot
+        ops.linearp_fwd(h, W, W16[-1], bt, P, bw, False, None, None, C=Xv, epilogue=ops.EPI_NONE)
+        ops.planes_rowdot(h, W, Wh[bw], bt[bw:bw + 1], density, p0=self.density_bias)
         ops.encode_viewdirs(viewdirs, S, Xv, bw)
         hv = torch.empty(P, self.netwidth_condition, device=dev)
         Wt, bt = self._w(self._views)

@@ -111,7 +111,7 @@ def linear_fwd(A0: torch.Tensor, K0: int, W: torch.Tensor, bias: Optional[torch.
     M = A0.shape[0] if M is None else M
     if epilogue == EPI_RESIDUAL:
         aux_col = aux.stride(0)
-    if (THIN_GEMM and rows_dev is None and A1 is None and 128 < N <= 256 and K0 <= 320 and K0 % 4 == 0 and M >= 16384 and epilogue in (EPI_NONE, EPI_RELU)
+    if (rows_dev is None and A1 is None and 128 < N <= 256 and K0 <= 320 and K0 % 4 == 0 and M >= 16384 and epilogue in (EPI_NONE, EPI_RELU)
             and ldc is None and out is not None and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3):
         # many rows through a thin layer: persistent kernel with the weight in registers (hos_thin.hip)
         _timed(f"thin_fwd[M={M},N={N},K={K0}]", 2.0 * M * N * K0, lambda: call(
@@ -128,7 +128,7 @@ def linear_fwd(A0: torch.Tensor, K0: int, W: torch.Tensor, bias: Optional[torch.
 
 
 # the canonical MLP with its per-call state embedding folded into the biases of the input layer and the skip layer (hos_thin.hip)
-CNL_FOLD = os.environ.get("HOS_CNL_FOLD", "1") != "0"
+CNL_FOLD = True
 _CNL_FOLD_WS = {}
 _ZERO1 = {}
 
@@ -252,10 +252,7 @@ def cnl_fold_grad_workspace(device, n_out: int, nfp: int, nh: int) -> torch.Tens
 def thin_dgrad_rows(M: int) -> bool:
     """True when `linear_dgrad` of a <= 256-wide layer over M rows runs on the thin kernel (which takes W / mask windows at any
     column; the tiled GEMMs need 16-byte aligned windows)."""
-    return bool(THIN_GEMM and M >= 16384 and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3)
-
-
-RELU_BITS = os.environ.get("HOS_RELU_BITS", "1") == "1"      # thin layers: ReLU mask of the backward pass as bits (A/B switch)
+    return bool(M >= 16384 and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3)
 
 
 def thin_relu_bits(M: int, device) -> torch.Tensor:
@@ -296,7 +293,7 @@ def linear_wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, db: Option
                  w_col0: int = 0, splits: int = 0):
     """dW[:N, w_col0:w_col0+K] += dY[:, :N]^T @ X[:, :K];  db[:N] += colsum(dY[:, :N])."""
     M = dY.shape[0]
-    if WGRAD_TR and 128 < N <= 256 and M >= 16384 and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3:
+    if 128 < N <= 256 and M >= 16384 and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3:
         # many rows, thin layer: staged-planes kernel with transposed LDS reads (hos_mlpbwd.hip), K in chunks of <= 256
         for k0 in range(0, K, 256):
             kc = min(256, K - k0)
@@ -357,7 +354,6 @@ def _bwd_workspace(device, M: int = 0, N: int = 0, K: int = 0, fused: bool = Fal
     return ws[off:off + need]
 
 
-BWD_DEFER = os.environ.get("HOS_DEFER_REDUCE", "1") != "0"
 BWD_DEFER_WS_FLOATS = 160 * 1024 * 1024       # 640 MB: the eight 256-wide layers of the canonical MLP (67 MB of slabs each) in one batch
 
 
@@ -366,7 +362,7 @@ class deferred_bwd_reduce:
     batched launch at the exit (hos_mlp_bwd_defer / hos_mlp_bwd_flush); dW / db are complete after the block."""
 
     def __enter__(self):
-        self.nested = _BWD_DEFER["on"] or not BWD_DEFER
+        self.nested = _BWD_DEFER["on"]
         if not self.nested:
             _BWD_DEFER["on"], _BWD_DEFER["offset"] = True, 0
             _lib.check(_lib.load().hos_mlp_bwd_defer(1), "hos_mlp_bwd_defer")
@@ -380,19 +376,18 @@ class deferred_bwd_reduce:
         return False
 
 
-FUSED_THIN_BWD = os.environ.get("HOS_FUSED_BWD", "1") != "0"
-WGRAD_TR = os.environ.get("HOS_WGRAD_TR", "1") != "0"
-ROWDOT_HEADS = os.environ.get("HOS_ROWDOT_HEADS", "1") != "0"      # one-column heads of the planes MLPs as a row dot (hos_planes_rowdot)
-THIN_GEMM = os.environ.get("HOS_THIN_GEMM", "1") != "0"
-WGRAD_WS = os.environ.get("HOS_WGRAD_WS", "1") == "1"       # planes WGRAD: split-K partials through the slab workspace
-WGRAD_WS_MIN = int(os.environ.get("HOS_WGRAD_WS_MIN", "0"))  # ... for gradients of at least this many elements
+# Retired A/B switches.  The one-pass 128-wide layer backward (linear_bwd_fused) and the wide weight gradient on hos_mlpbwd.hip
+# (hos_linear_wgrad_tr) are the only paths and nothing in this package reads these names; they stay defined, always True, because
+# callers written against the previous revision assert them before relying on those paths (`assert ops.WGRAD_TR`).
+FUSED_THIN_BWD = True
+WGRAD_TR = True
 
 
 # ------------------------------------------------------------------------------------------ fused MLP chain (hos_chain.hip)
-MLP_CHAIN = os.environ.get("HOS_MLP_CHAIN", "1") != "0"
-MLP_CHAIN_MIN_ROWS = int(os.environ.get("HOS_MLP_CHAIN_MIN_ROWS", "4096"))
+MLP_CHAIN = True
+MLP_CHAIN_MIN_ROWS = 4096
 # the non-rigid chain with the per-frame condition code folded into the first layer's bias (hos_chain.hip, FOLD)
-MLP_CHAIN_FOLD = os.environ.get("HOS_CHAIN_FOLD", "1") != "0"
+MLP_CHAIN_FOLD = True
 _FOLD_WS = {}
 
 
@@ -404,8 +399,8 @@ def fold_grad_workspace(device) -> torch.Tensor:
         _FOLD_WS[key] = torch.empty(128 * 64 + 128, device=device)
     return _FOLD_WS[key]
 # ---- backward of the non-rigid MLP as three group launches, dZ on chip between the layers of a group (hos_mlpbwd.hip, chain_bwd_kernel)
-MLP_CHAIN_BWD = os.environ.get("HOS_CHAIN_BWD", "1") != "0"
-MLP_CHAIN_BWD_MIN_ROWS = int(os.environ.get("HOS_CHAIN_BWD_MIN_ROWS", "16384"))
+MLP_CHAIN_BWD = True
+MLP_CHAIN_BWD_MIN_ROWS = 16384
 _CB_IMAGES = {}
 _CB_IMAGES_MAX = 16        # (key, groups, device, stream) entries kept; oldest evicted first (buffers are repacked every backward)
 
@@ -1624,9 +1619,6 @@ def unbind_frames_many(*xs):
     return out
 
 
-SAMPLE_WARP_BWD_REUSE = os.environ.get("HOS_SAMPLE_WARP_BWD_REUSE", "1") == "1"   # A/B switch: backward reads the forward's x_skel / mask
-
-
 class _SampleWarp(torch.autograd.Function):
     """(z, pts, x_skel, mask) with gradients to the motion-weight volume and the backward motion basis."""
 
@@ -1651,7 +1643,7 @@ class _SampleWarp(torch.autograd.Function):
         scratch = torch.empty(P, 2, device=pts.device)
         call("hos_human_sample_warp_bwd", ptr(pts), ptr(R), ptr(T), ptr(vol), vol.shape[-1], ptr(bmin), ptr(bscale), P, K,
              ptr(gx), ptr(gm), ptr(g_vol), ptr(g_R), ptr(g_T), ptr(scratch),
-             ptr(x_skel) if SAMPLE_WARP_BWD_REUSE else None, ptr(mask) if SAMPLE_WARP_BWD_REUSE else None)
+             ptr(x_skel), ptr(mask))
         return g_vol, g_R, g_T, None, None, None, None, None, None, None, None, None
 
 
@@ -1874,10 +1866,10 @@ def _wgrad_workspace(device: torch.device) -> torch.Tensor:
 def linearp_wgrad(dZ: Planes, X: Planes, dW: torch.Tensor, db, M: int, N: int, K: int, w_col0: int = 0, splits: int = 0,
                   x_col0: int = 0, use_ws: bool = False):
     """dW[:, w_col0:w_col0+K] += dZ^T @ X[:, x_col0:x_col0+K]; db += column sums of dZ (row-major bf16 planes).
-    The split-K partial tiles go through a slab workspace and are summed in a fixed order by default (bit-reproducible and,
-    with the eight-loads-per-round reduce kernel, ~1 % faster on the stage-1 step than fp32 atomics); HOS_WGRAD_WS=0 selects
-    the atomics."""
-    ws = _wgrad_workspace(dW.device) if (use_ws or (WGRAD_WS and N * K >= WGRAD_WS_MIN)) else None
+    The split-K partial tiles always go through a slab workspace and are summed in a fixed order (bit-reproducible and, with the
+    eight-loads-per-round reduce kernel, ~1 % faster on the stage-1 step than fp32 atomics).  `use_ws` is IGNORED: it remains in
+    the signature for existing callers only."""
+    ws = _wgrad_workspace(dW.device)
     _timed(f"gemmp_wgrad[M={N},N={K},K={M}]", 2.0 * M * N * K, lambda: call(
         "hos_linearp_wgrad", _pp(dZ), dZ.ld, _pp(X), X.ld, x_col0,
-        ptr(dW) + 4 * w_col0, dW.stride(0), ptr(db), M, N, K, splits, ptr(ws), 0 if ws is None else ws.numel()))
+        ptr(dW) + 4 * w_col0, dW.stride(0), ptr(db), M, N, K, splits, ptr(ws), ws.numel()))

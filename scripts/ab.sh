@@ -1,6 +1,6 @@
 #!/bin/bash
 # Step-level A/B of one runtime switch, alternated REPS times so that box drift shows up as spread, not as a result:
-#   scripts/ab.sh HOS_PERSIST_GRID "256 384 512" [REPS] [-- extra bench.py args]
+#   scripts/ab.sh HOS_TWO_STREAMS "0 1" [REPS] [-- extra bench.py args]
 # prints ms/step of stage 2 (2048 rays), stage 3 (4096 rays) and stage 3 at 512 rays (one rank's share at N = 8) per value.
 VAR=$1; VALUES=$2; REPS=${3:-3}; shift 3 2>/dev/null; [ "$1" = "--" ] && shift
 cd ${GRAFT_REPO_ROOT:-/root/repo}

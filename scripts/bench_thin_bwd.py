@@ -1,5 +1,5 @@
 """Microbenchmark of hos_linear_bwd_fused (mlp_bwd_kernel<4,4,true>) and its slab reduction over the row count:
-fixed cost per launch vs per-row slope.  Usage: python scripts/bench_thin_bwd.py [grid override via HOS_MB_GRID]"""
+fixed cost per launch vs per-row slope.  Usage: python scripts/bench_thin_bwd.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

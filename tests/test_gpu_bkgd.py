@@ -534,7 +534,7 @@ def test_planes_gemm_matches_fp64(M, N, K):
     assert (dX.float().double() - refd).abs().max().item() < 2e-4 * refd.abs().max().item() + 1e-5
     dW = torch.zeros(N, K, device=dev); db = torch.zeros(N, device=dev)
     refw = dY.double().T @ X.double()
-    for use_ws in (True, False):             # slab reduction through the workspace / fp32 atomics
+    for use_ws in (True, False):             # the argument is ignored: both passes take the slab reduction through the workspace
         dW.zero_(); db.zero_()
         ops.linearp_wgrad(dZ, Xb, dW, db, M, N, K, use_ws=use_ws)
         assert (dW.double() - refw).abs().max().item() < 2e-4 * refw.abs().max().item()

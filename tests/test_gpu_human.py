@@ -289,7 +289,7 @@ def test_gradients_vs_oracle(dev, net, group_bwd):
     torch autograd) against the oracle's autograd on the same random cotangents."""
     from hosnerf_amd import ops
     if group_bwd:
-        assert ops.MLP_CHAIN and ops.MLP_CHAIN_FOLD and ops.MLP_CHAIN_BWD and ops.FUSED_THIN_BWD, "group backward is the default path"
+        assert ops.MLP_CHAIN and ops.MLP_CHAIN_FOLD and ops.MLP_CHAIN_BWD, "group backward is the default path"
     b = synth.human_batch(8, seed=21, time=0.5, is_train=True, iter_val=3e5)
     sd = {k: v.clone().requires_grad_(True) for k, v in synth.human_state_dict(777, 2).items()}
     out_o = oh.human_forward(sd, b, transitions_times=[0.4])
@@ -423,7 +423,6 @@ def test_linear_wgrad_tr(dev, M, N, K, wcol0, ldw):
     """hos_linear_wgrad_tr (the route ops.linear_wgrad takes for 128 < N <= 256 and many rows) against fp64."""
     from hosnerf_amd import ops
     ops.set_gemm_mode(ops.GEMM_PLANES)       # the routes under test are taken in the split-precision modes only
-    assert ops.WGRAD_TR
     g = torch.Generator().manual_seed(M + K)
     Np = (N + 31) // 32 * 32
     dY = torch.zeros(M, Np)

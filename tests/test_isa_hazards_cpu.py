@@ -25,8 +25,7 @@ def test_chain_kernels_never_touch_an_inflight_fragment():
 
 
 def test_planes_gemm_main_loops_never_touch_an_inflight_fragment():
-    """All twelve instantiations of the default build (round 5: + bf16-operand FWD; the persistent FWD / DGRAD forms are compiled out
-    by default, -DHOS_GEMMP_PERSIST=1 adds three); the scan covers the main loop (first to last MFMA)."""
+    """All twelve instantiations of the build (round 5: + bf16-operand FWD); the scan covers the main loop (first to last MFMA)."""
     import scan_inflight_reads as S
     rep = S.scan(os.path.join(ROOT, "hosnerf_amd", "csrc", "hos_gemmp.hip"), ["gemmp_kernel"], region="mfma")
     assert len(rep) == 12, list(rep)
