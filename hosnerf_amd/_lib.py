@@ -37,14 +37,18 @@ PROTOTYPES = {
     "hos_linear_fwd_splitk_det": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _L, _P],
     "hos_linear_dgrad": [_P, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P],
     "hos_linear_wgrad": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
+    "hos_linear_wgrad_rows": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P],
     "hos_thin_linear_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "hos_thin_linear_dgrad": [_P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P],
+    "hos_thin_linear_fwd_rows": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "hos_thin_linear_dgrad_rows": [_P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P],
     "hos_canonical_fold_pack": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "hos_canonical_fold_unfold": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "hos_mlp_bwd_defer": [_I],
     "hos_mlp_bwd_flush": [_P],
     "hos_mlp_bwd_ws_floats": [_I, _I, _I, _I],
     "hos_linear_wgrad_tr": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _L, _P],
+    "hos_linear_wgrad_tr_rows": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _L, _P, _P],
     "hos_linear_bwd_fused": [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _L, _P, _P],
     "hos_stage1_loss_fwd": [_P, _P, _I, _P, _P, _I, _P, _F, _F, _F, _F, _P, _P],
     "hos_stage1_loss_bwd": [_P, _P, _I, _I, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P],
@@ -101,12 +105,14 @@ PROTOTYPES = {
     "hos_lbs_forward": [_P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _P, _P, _P],
     "hos_embed_hannw": [_P, _P, _I, _P, _I, _L, _P, _I, _P, _I, _P, _P],
     "hos_embed_fourier": [_P, _I, _P, _I, _L, _P, _I, _P, _I, _P],
+    "hos_embed_fourier_rows": [_P, _I, _P, _I, _L, _P, _I, _P, _I, _P, _P],
     "hos_human_sample_warp_bwd": [_P, _P, _P, _P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hos_lbs_forward_bwd": [_P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P],
     "hos_embed_bwd": [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _L, _P, _I, _P, _P],
     "hos_slice_mask": [_P, _I, _I, _P, _I, _I, _L, _I, _P, _I, _P, _P],
     "hos_slice_pad": [_P, _I, _I, _L, _I, _P, _I, _P, _P],
     "hos_rgbsigma_grad": [_P, _P, _L, _P, _I, _P],
+    "hos_rgbsigma_grad_rows": [_P, _P, _L, _P, _I, _P, _P],
     "hos_raw2outputs_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P],
     "hos_raw2outputs_bwd": [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _F, _I, _I, _P, _I, _P, _I, _P, _P],
     "hos_merge_composite_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
@@ -126,6 +132,9 @@ PROTOTYPES = {
     "hos_compact_workspace_ints": [],
     "hos_compact_rows": [_P, _F, _P, _P, _L, _P, _P, _P, _P, _P, _P],
     "hos_scatter_rows": [_P, _P, _P, _L, _P, _P],
+    "hos_select_live_rays": [_P, _F, _I, _I, _P, _P, _P, _P],
+    "hos_gather_rays": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "hos_scatter_rays": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
     "hos_pose_refine_saved_floats": [],
     "hos_pose_refine_fwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "hos_pose_refine_workspace_floats": [],

@@ -50,6 +50,15 @@ __device__ __forceinline__ float wave_incl_rscan(float v, int lane) {
     return v;
 }
 
+// The foreground decision of a stage-3 ray (M:1547-1551: sum_s pts_mask[ray, s] > thr), taken by one wavefront: lane-strided
+// partial sums s = lane, lane + 64, ... then wave_sum.  merge_composite_kernel and live_flag_kernel (hos_compact.hip) both call
+// THIS function: a ray the two classified differently would be composited with zeros for its human samples.
+__device__ __forceinline__ bool ray_is_foreground(const float* __restrict__ mask, int ray, int Sh, float thr, int lane) {
+    float msum = 0.f;
+    for (int s = lane; s < Sh; s += 64) msum += mask[(size_t)ray * Sh + s];
+    return wave_sum(msum) > thr;
+}
+
 __device__ __forceinline__ float softplus_f(float x) {
     // torch.nn.Softplus(beta=1, threshold=20)
     return x > 20.f ? x : log1pf(expf(x));

@@ -8,6 +8,14 @@
 //   hos_scatter_rows      dst[sel[j]] = src[j] for j < count, every other row of dst zero (the gather's gradient)
 //
 // Two launches: per-block counts + an exclusive scan by the last block to finish, then the scatter pass.
+//
+// Ray-level form for stage-3 training (M:1547-1551: a ray whose mask sum is <= thr is composited from its background samples
+// alone, so nothing behind the backward warp is needed for it):
+//
+//   hos_select_live_rays  flag[ray] = the merge kernel's own foreground decision (ray_is_foreground, hos_common.h);
+//                         ray_ids = ascending indices of the foreground rays, then -1; *rows_live = n_live * S
+//   hos_gather_rays       dst[j] = src[ray_ids[j / S] * S + j % S] for j < *rows_live, rows behind it zero
+//   hos_scatter_rays      the inverse: rows of foreground rays from the front of src, rows of background rays zero
 #include "hos_common.h"
 
 namespace {
@@ -122,7 +130,110 @@ __global__ __launch_bounds__(CT) void scatter_rows_kernel(const float* src, cons
     }
 }
 
+// ---- ray-level selection ------------------------------------------------------------------------------------------------
+constexpr int LT = 1024;           // threads of the single scan block
+
+__global__ __launch_bounds__(256) void live_flag_kernel(const float* __restrict__ mask, float thr, int B, int S, int* __restrict__ flag) {
+    const int lane = threadIdx.x & 63, ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= B) return;                                      // wave-uniform
+    const bool fg = ray_is_foreground(mask, ray, S, thr, lane);
+    if (lane == 0) flag[ray] = fg ? 1 : 0;
+}
+
+// one block: exclusive scan of flag[B] (thread t owns rays t * per .. t * per + per - 1: ascending order is kept)
+__global__ __launch_bounds__(LT) void live_scan_kernel(const int* __restrict__ flag, int B, int S, int* __restrict__ ray_ids,
+                                                       int* __restrict__ rows_live) {
+    __shared__ int wsum[LT / 64];
+    __shared__ int total;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int per = (B + LT - 1) / LT;
+    const int r0 = t * per;
+    int c = 0;
+    for (int k = 0; k < per; ++k) c += (r0 + k < B && flag[r0 + k] != 0) ? 1 : 0;
+    int incl = c;
+    for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(incl, o, 64); if (lane >= o) incl += n; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int pos = incl - c;
+    for (int w = 0; w < wave; ++w) pos += wsum[w];
+    if (t == LT - 1) { total = pos + c; *rows_live = (pos + c) * S; }
+    for (int k = 0; k < per; ++k)
+        if (r0 + k < B && flag[r0 + k] != 0) ray_ids[pos++] = r0 + k;
+    __syncthreads();
+    const int n = total;
+    for (int i = n + t; i < B; i += LT) ray_ids[i] = -1;
+}
+
+// one thread per element: dst row j (compact) <- src row of its ray; rows >= *rows_live are zero
+__global__ __launch_bounds__(256) void gather_rays_kernel(const float* __restrict__ src, const int* __restrict__ ray_ids,
+                                                         const int* __restrict__ rows_live, long P, int S, int C, float* __restrict__ dst) {
+    const long total = P * C;
+    const long live = min((long)*rows_live, P) * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        float v = 0.f;
+        if (i < live) {
+            const long j = i / C;
+            const int c = (int)(i - j * C);
+            const long ray = ray_ids[j / S];
+            v = src[(ray * S + j % S) * C + c];
+        }
+        dst[i] = v;
+    }
+}
+
+// element i of the FULL buffer: its ray is live -> it is written by the thread that owns the matching compact element; dead -> zero.
+// Every thread therefore does two things for its index i: (compact element i, if live) -> its place, and (full element i, if its
+// ray is dead) -> 0.  The two destination sets are disjoint and together cover dst.
+__global__ __launch_bounds__(256) void scatter_rays_kernel(const float* __restrict__ src, const int* __restrict__ ray_ids,
+                                                          const int* __restrict__ flag, const int* __restrict__ rows_live, long P, int S,
+                                                          int C, float* __restrict__ dst) {
+    const long total = P * C;
+    const long live = min((long)*rows_live, P) * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long j = i / C;
+        const int c = (int)(i - j * C);
+        if (i < live) {
+            const long ray = ray_ids[j / S];
+            dst[(ray * S + j % S) * C + c] = src[i];
+        }
+        if (flag[j / S] == 0) dst[i] = 0.f;
+    }
+}
+
+inline int rays_grid(long total) {
+    long b = (total + 255) / 256;
+    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+
 }  // namespace
+
+extern "C" int hos_select_live_rays(const float* mask, float thr, int B, int S, int32_t* ray_ids, int32_t* flag, int32_t* rows_live,
+                                    hos_stream_t stream) {
+    if (!mask || !ray_ids || !flag || !rows_live || B <= 0 || S <= 0) return HOS_E_ARG;
+    if ((long long)B * S > 0x7fffffffLL) return HOS_E_SHAPE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(live_flag_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, mask, thr, B, S, flag);
+    hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(LT), 0, s, flag, B, S, ray_ids, rows_live);
+    return hos_launch_status();
+}
+
+extern "C" int hos_gather_rays(const float* src, const int32_t* ray_ids, const int32_t* rows_live, int B, int S, int C, float* dst,
+                               hos_stream_t stream) {
+    if (!src || !ray_ids || !rows_live || !dst || B <= 0 || S <= 0 || C <= 0) return HOS_E_ARG;
+    const long P = (long)B * S;
+    hipLaunchKernelGGL(gather_rays_kernel, dim3(rays_grid(P * C)), dim3(256), 0, static_cast<hipStream_t>(stream), src, ray_ids, rows_live,
+                       P, S, C, dst);
+    return hos_launch_status();
+}
+
+extern "C" int hos_scatter_rays(const float* src, const int32_t* ray_ids, const int32_t* flag, const int32_t* rows_live, int B, int S,
+                                int C, float* dst, hos_stream_t stream) {
+    if (!src || !ray_ids || !flag || !rows_live || !dst || B <= 0 || S <= 0 || C <= 0) return HOS_E_ARG;
+    const long P = (long)B * S;
+    hipLaunchKernelGGL(scatter_rays_kernel, dim3(rays_grid(P * C)), dim3(256), 0, static_cast<hipStream_t>(stream), src, ray_ids, flag,
+                       rows_live, P, S, C, dst);
+    return hos_launch_status();
+}
 
 extern "C" long long hos_compact_workspace_ints(void) { return CMAXB + 4; }
 

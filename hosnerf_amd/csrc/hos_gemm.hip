@@ -106,7 +106,14 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const GemmArgs a) {
     const int i0 = tm_i * BM, j0 = tn_i * BN;
     if (MODE == MODE_FWD && a.m_dev && i0 >= *a.m_dev) return;     // fixed-capacity buffer: rows past the device-side count are dead
     const int kt_begin = split * a.kt_per_split;
-    const int kt_end = min(a.nk, kt_begin + a.kt_per_split);
+    int kt_end = min(a.nk, kt_begin + a.kt_per_split);
+    // WGRAD over a fixed-capacity buffer: reduction rows at and behind the device-side count are uninitialised memory -- the
+    // loaders zero-fill them WITHOUT reading (red_limit), and a split that lies wholly behind the count adds nothing
+    int red_limit = a.red_limit;
+    if (MODE == MODE_WGRAD && a.m_dev) {
+        red_limit = min(red_limit, *a.m_dev);
+        kt_end = min(kt_end, (red_limit + BK - 1) / BK);
+    }
     if (kt_begin >= kt_end) return;
 
     f32x16 acc[TM][TN];
@@ -127,14 +134,14 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const GemmArgs a) {
             if (MODE == MODE_FWD && kt >= a.kt0) { P = a.A1; ld = a.lda1; k0 = (kt - a.kt0) * BK; }
             load_kc<BM>(ra, P, ld, i0, a.Mload, k0, t);
         } else {
-            load_rc<BM>(ra, a.A0, a.lda0, i0, a.Mload, kt * BK, t, a.red_limit);
+            load_rc<BM>(ra, a.A0, a.lda0, i0, a.Mload, kt * BK, t, red_limit);
             if (do_db) {
 #pragma unroll
                 for (int r = 0; r < BM / 32; ++r) { bsum.x += ra[r].x; bsum.y += ra[r].y; bsum.z += ra[r].z; bsum.w += ra[r].w; }
             }
         }
         if constexpr (B_KC) load_kc<BN>(rb, a.B, a.ldb, j0, a.Nload, kt * BK, t);
-        else                load_rc<BN>(rb, a.B, a.ldb, j0, a.Nload, kt * BK, t, a.red_limit);
+        else                load_rc<BN>(rb, a.B, a.ldb, j0, a.Nload, kt * BK, t, red_limit);
     };
     auto sstore = [&](int buf) {
         if constexpr (A_KC) store_kc<BM, LDA>(ra, As + buf * BK * LDA, t);
@@ -453,9 +460,12 @@ extern "C" int hos_linear_dgrad(const float* dY, int lddy, const float* W, int l
     return launch<128, 128, MODE_DGRAD>(a, 1, s);
 }
 
-extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
-                                float* db, int M, int N, int K, int splits, hos_stream_t stream) {
+// rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows enter the sums; the rest is not read.
+// Narrow layers only (N <= 32: the canonical head, whose WGRAD runs on this file's exact-fp32 kernel in every arithmetic mode).
+extern "C" int hos_linear_wgrad_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
+                                     float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream) {
     if (!dY || !X || !dW || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
+    if (rows_dev && N > 32) return HOS_E_SHAPE;
     if ((lddy & 3) || (ldx & 3) || (K & 3)) return HOS_E_ALIGN;
     if (!al16(dY) || !al16(X)) return HOS_E_ALIGN;
     GemmArgs a{};
@@ -466,6 +476,7 @@ extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int l
     a.Nload = K;
     a.nk = hos_cdiv(M, BK);          // rows >= M are zero-filled by the loaders (red_limit)
     a.red_limit = M;
+    a.m_dev = rows_dev;
     a.db = db;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool narrow = (N <= 32);
@@ -482,4 +493,9 @@ extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int l
     splits = hos_cdiv(a.nk, a.kt_per_split);
     if (narrow) return launch<32, 128, MODE_WGRAD>(a, splits, s);
     return launch<128, 128, MODE_WGRAD>(a, splits, s);
+}
+
+extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
+                                float* db, int M, int N, int K, int splits, hos_stream_t stream) {
+    return hos_linear_wgrad_rows(dY, lddy, X, ldx, dW, ldw, db, M, N, K, splits, nullptr, stream);
 }

@@ -25,7 +25,8 @@ struct GemmArgs {
     float* db;
     int accumulate;
     int epi;
-    const int* m_dev;        // FWD only, optional: live row count in device memory; row tiles at or past it are skipped
+    const int* m_dev;        // optional: live row count in device memory.  FWD: row tiles at or past it are skipped; WGRAD
+                             // (hos_gemm.hip only): reduction rows at or past it are zero-filled without being read
     unsigned int* range_flag;   // FWD, optional: set to 1 when a hidden activation leaves the exactly-representable fp16 hi/lo range
 };
 

@@ -182,7 +182,9 @@ __global__ __launch_bounds__(256) void embed_hannw_kernel(const float* __restric
 // [x(3), sin(2^j x), cos(2^j x) (j < F)] | state embedding (NE) | 0-pad; optional second destination E2.
 __global__ __launch_bounds__(256) void embed_fourier_kernel(const float* __restrict__ x, int F,
                                                             const float* __restrict__ state, int NE, long P,
-                                                            float* __restrict__ E, int lde, float* __restrict__ E2, int lde2) {
+                                                            float* __restrict__ E, int lde, float* __restrict__ E2, int lde2,
+                                                            const int* __restrict__ p_dev) {
+    if (p_dev) P = min(P, (long)*p_dev);
     const long total = P * lde;
     const int nf = 3 + 6 * F;
     for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
@@ -256,8 +258,10 @@ __global__ __launch_bounds__(256) void embed_hannw_tiled_kernel(const float* __r
 
 __global__ __launch_bounds__(256) void embed_fourier_tiled_kernel(const float* __restrict__ x, int F,
                                                                   const float* __restrict__ state, int NE, long P,
-                                                                  float* __restrict__ E, int lde, float* __restrict__ E2, int lde2) {
+                                                                  float* __restrict__ E, int lde, float* __restrict__ E2, int lde2,
+                                                                  const int* __restrict__ p_dev) {
     __shared__ float sF[EM_RB][EM_FMAX + 1];
+    if (p_dev) P = min(P, (long)*p_dev);
     const int t = threadIdx.x, nf = 3 + 6 * F, nv = nf + NE;      // nv = columns that carry a value
     for (long row0 = (long)blockIdx.x * EM_RB; row0 < P; row0 += (long)gridDim.x * EM_RB) {
         const int rows = (int)min((long)EM_RB, P - row0);
@@ -352,19 +356,25 @@ extern "C" int hos_embed_hannw(const float* x, const float* band_w, int num_freq
     return hos_launch_status();
 }
 
-extern "C" int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
-                                 float* E, int lde, float* E2, int lde2, hos_stream_t stream) {
+// rows_dev (optional, int32 [1] in device memory): only the first min(P, *rows_dev) rows are read and written.
+extern "C" int hos_embed_fourier_rows(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
+                                      float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream) {
     if (!x || !E || P <= 0 || (state_size > 0 && !state)) return HOS_E_ARG;
     if (num_freqs < 1 || num_freqs > 16 || lde < 3 + 6 * num_freqs + state_size) return HOS_E_SHAPE;
     if (E2 && lde2 < 3 + 6 * num_freqs + state_size) return HOS_E_SHAPE;
     if (!(lde & 3) && em_al16(E) && (!E2 || (!(lde2 & 3) && em_al16(E2))) && 3 + 6 * num_freqs <= EM_FMAX) {
         hipLaunchKernelGGL(embed_fourier_tiled_kernel, dim3(em_grid(P)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           x, num_freqs, state, state_size, (long)P, E, lde, E2, lde2);
+                           x, num_freqs, state, state_size, (long)P, E, lde, E2, lde2, rows_dev);
         return hos_launch_status();
     }
     hipLaunchKernelGGL(embed_fourier_kernel, dim3(grid_for(P * lde)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x, num_freqs, state, state_size, (long)P, E, lde, E2, lde2);
+                       x, num_freqs, state, state_size, (long)P, E, lde, E2, lde2, rows_dev);
     return hos_launch_status();
+}
+
+extern "C" int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
+                                 float* E, int lde, float* E2, int lde2, hos_stream_t stream) {
+    return hos_embed_fourier_rows(x, num_freqs, state, state_size, P, E, lde, E2, lde2, nullptr, stream);
 }
 
 // ================================================================================================
@@ -899,7 +909,8 @@ __global__ __launch_bounds__(256) void slice_mask_kernel(const float* __restrict
 // d(pre-activation) of the canonical head: cols 0..2 sigmoid' = s(1-s), col 3 relu'; the whole [P, ldo] row is written
 // (16 bytes per thread, columns 4.. zero): the caller passes uninitialised storage, no fill launch
 __global__ __launch_bounds__(256) void rgbsigma_grad_kernel(const float* __restrict__ g, const float* __restrict__ y, long P,
-                                                            float* __restrict__ out, int ldo) {
+                                                            float* __restrict__ out, int ldo, const int* __restrict__ p_dev) {
+    if (p_dev) P = min(P, (long)*p_dev);
     const int q = ldo >> 2;
     const long total = P * q;
     for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
@@ -1019,13 +1030,19 @@ extern "C" int hos_slice_mask(const float* src, int lds, int col0, const float* 
     return hos_launch_status();
 }
 
-extern "C" int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
-                                 hos_stream_t stream) {
+// rows_dev (optional, int32 [1] in device memory): only the first min(P, *rows_dev) rows are read and written.
+extern "C" int hos_rgbsigma_grad_rows(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
+                                      const int32_t* rows_dev, hos_stream_t stream) {
     if (!g_rgbsigma || !rgbsigma || !dz || P <= 0 || ldz < 4) return HOS_E_ARG;
     if ((ldz & 3) || (((uintptr_t)g_rgbsigma | (uintptr_t)rgbsigma | (uintptr_t)dz) & 15u)) return HOS_E_ALIGN;
     hipLaunchKernelGGL(rgbsigma_grad_kernel, dim3(grid_for(P * (ldz >> 2))), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       g_rgbsigma, rgbsigma, (long)P, dz, ldz);
+                       g_rgbsigma, rgbsigma, (long)P, dz, ldz, rows_dev);
     return hos_launch_status();
+}
+
+extern "C" int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
+                                 hos_stream_t stream) {
+    return hos_rgbsigma_grad_rows(g_rgbsigma, rgbsigma, P, dz, ldz, nullptr, stream);
 }
 
 extern "C" int hos_slice_pad(const float* src, int lds, int col0, int64_t P, int width, float* out, int ldo,

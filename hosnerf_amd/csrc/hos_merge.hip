@@ -188,7 +188,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const Args a) {
     const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
     const bool first_comp = a.tiny_d_flag != nullptr && *a.tiny_d_flag != 0;
     // C1: human sample depth along the background ray (M:1524, :1526-1545)
-    float msum = 0.f;
     for (int s = lane; s < Sh; s += 64) {
         const float* p = a.pts + ((size_t)ray * Sh + s) * 3;
         const float wx = a.A[0] * p[0] + a.A[1] * p[1] + a.A[2] * p[2] + a.A[3];
@@ -204,11 +203,9 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const Args a) {
         }
         L.key[Sb + s] = zh;
         if (a.z_h && live) a.z_h[(size_t)ray * Sh + s] = zh;
-        msum += a.mask[(size_t)ray * Sh + s];
     }
     for (int s = lane; s < Sb; s += 64) L.key[s] = a.bkg_tdist[(size_t)ray * (Sb + 1) + s];
-    msum = wave_sum(msum);
-    const bool fg = msum > a.thre_fg;                                                   // M:1547-1551
+    const bool fg = ray_is_foreground(a.mask, ray, Sh, a.thre_fg, lane);               // M:1547-1551 (shared with hos_select_live_rays)
     __syncthreads();
     const int S = fg ? St : Sb;
     if (fg) {

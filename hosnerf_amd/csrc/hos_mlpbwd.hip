@@ -342,7 +342,7 @@ __global__ __launch_bounds__(MB_NT, 1) void wgrad_tr_fast_kernel(MlpBwdArgs a) {
     const int tr_col = 16 * (tr_g & 1) + 4 * (tr_p & 3);
     const bool xthread = XALL || t < XT;
 
-    const int nrb = a.M / R;
+    const int nrb = (a.m_dev ? min(a.M, *a.m_dev) : a.M) / R;   // live row blocks (device-side bound: a multiple of 32 by contract)
     const int G = gridDim.x;
     float4 rzA[ZU], rxA[XU], rzB[ZU], rxB[XU];
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -415,20 +415,24 @@ __global__ __launch_bounds__(MB_NT, 1) void wgrad_tr_fast_kernel(MlpBwdArgs a) {
         compute();
         WG_BAR();
     };
-    int rb = blockIdx.x;                                                       // grid <= nrb
-    gload(rzA, rxA, rb);
-    gload(rzB, rxB, rb + G);
-    step(rzA, rxA, rb);
-    rb += G;
+    int rb = blockIdx.x;
+    // A workgroup past the live row blocks (device-side bound) loads nothing -- the rows there are uninitialised memory -- and
+    // writes its zero slab and zero db partial below: the reduce launch sums `grid` slabs.  Block-uniform.
     if (rb < nrb) {
-        step(rzB, rxB, rb);
+        gload(rzA, rxA, rb);
+        gload(rzB, rxB, rb + G);
+        step(rzA, rxA, rb);
         rb += G;
-        while (rb + G < nrb) {
-            step(rzA, rxA, rb);
-            step(rzB, rxB, rb + G);
-            rb += 2 * G;
+        if (rb < nrb) {
+            step(rzB, rxB, rb);
+            rb += G;
+            while (rb + G < nrb) {
+                step(rzA, rxA, rb);
+                step(rzB, rxB, rb + G);
+                rb += 2 * G;
+            }
+            if (rb < nrb) step(rzA, rxA, rb);
         }
-        if (rb < nrb) step(rzA, rxA, rb);
     }
 #undef WG_BAR
     // ---- dW / db partials of this workgroup -> its slab (summed by the reduce kernel)
@@ -583,7 +587,7 @@ int launch_wgrad_fast(MlpBwdArgs a, size_t ws_floats, hipStream_t stream) {
     constexpr size_t smem = 2 * (size_t)R * (N_ * 2 + 32) + 2 * (size_t)R * (K_ * 2 + 32);
     const int nrb = a.M / R;
     const int grid = nrb < 256 ? nrb : 256;
-    if (a.M % R != 0 || a.N != N_ || a.K != K_ || a.m_dev != nullptr || a.ws == nullptr || grid < 32 ||
+    if (a.M % R != 0 || a.N != N_ || a.K != K_ || a.ws == nullptr || grid < 32 ||
         ws_floats < (size_t)grid * (nk + N_) || (((uintptr_t)a.ws) & 15u)) return -1;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1051,13 +1055,15 @@ extern "C" int hos_linear_bwd_fused(const float* dZ, int lddz, const float* X, i
 // transposes): dW [N, lddw] += dZ^T . X, db [N] += column sums.  N <= 256, K <= 256, K % 4 == 0.  The split-K partials of
 // the 256 workgroups (and their db partials) go through `ws` (>= 256*(256*256+256) floats = 67 MB; NULL or smaller: fp32 atomics,
 // measured 72 us of fixed cost per launch against ~30 us for the slab write + reduce).
-extern "C" int hos_linear_wgrad_tr(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
-                                   int M, int N, int K, float* ws, int64_t ws_floats, hos_stream_t stream) {
+// rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows enter the sums (a multiple of 32 by
+// contract; rows behind it are not read).  The launch shape -- grid, slabs, reduce -- is that of the capacity M.
+extern "C" int hos_linear_wgrad_tr_rows(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
+                                        int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream) {
     if (!dZ || !X || !dW || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
     if (N > 256 || K > 256) return HOS_E_SHAPE;
     if ((lddz & 3) || (ldx & 3) || (K & 3)) return HOS_E_ALIGN;
     if (((uintptr_t)dZ | (uintptr_t)X) & 15u) return HOS_E_ALIGN;
-    MlpBwdArgs a{dZ, lddz, X, ldx, nullptr, 0, nullptr, 0, dW, lddw, db, M, N, K, 0, ws, 0};
+    MlpBwdArgs a{dZ, lddz, X, ldx, nullptr, 0, nullptr, 0, dW, lddw, db, M, N, K, 0, ws, 0, rows_dev};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int kt = hos_cdiv(K, 32);
     if (N == 256 && (K == 256 || K == 64)) {        // the canonical MLP's layers (and the 64-column Fourier rows of its folded input)
@@ -1066,6 +1072,11 @@ extern "C" int hos_linear_wgrad_tr(const float* dZ, int lddz, const float* X, in
     }
     if (kt <= 4) return launch_mb<8, 4, false>(a, (size_t)ws_floats, s);
     return launch_mb<8, 8, false>(a, (size_t)ws_floats, s);
+}
+
+extern "C" int hos_linear_wgrad_tr(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
+                                   int M, int N, int K, float* ws, int64_t ws_floats, hos_stream_t stream) {
+    return hos_linear_wgrad_tr_rows(dZ, lddz, X, ldx, dW, lddw, db, M, N, K, ws, ws_floats, nullptr, stream);
 }
 
 // Deferred slab reductions: between hos_mlp_bwd_defer(1) and hos_mlp_bwd_flush() every hos_linear_bwd_fused /

@@ -50,7 +50,12 @@ struct ThinArgs {
     unsigned int* range_flag;         // FWD: see HOS_RANGE_LIMIT
     uint16_t* bits;                   // ReLU bit mask [ceil(M/32)][8 waves][64 lanes] x 16 bits (FWD: written; DGRAD: read instead of
                                       // `mask`), bit 15 - (4 g + k) of a lane = the element it owns after the quad transpose (NULL: none)
+    const int* m_dev;                 // optional: live row count in device memory (fixed-capacity buffers; a multiple of 32 by contract).
+                                      // Rows at and behind it are neither read nor written: they are uninitialised memory.
 };
+
+// whole 32-row tiles below the device-side bound (read once, at kernel entry)
+__device__ __forceinline__ int th_live_tiles(const ThinArgs& a) { return (a.m_dev ? min(a.M, *a.m_dev) : a.M) / 32; }
 
 constexpr int TH_NT = 512;
 // Row padding of the (hi, lo) planes in LDS.  A fragment read is ds_read_b128 at row (lane & 31), 16-byte piece 2 s + (lane >> 5);
@@ -66,7 +71,8 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 
 // KS: reduction steps of 16 (K <= 16 KS).  R: rows per tile (64 FWD, 32 DGRAD: the mask tile needs the registers).
 template <int KS, bool DGRAD>
-__global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(const ThinArgs a) {
+__global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
+    if (a.m_dev) a.M = min(a.M, *a.m_dev);               // every row test below then stops at the live rows
     typedef typename std::conditional<DGRAD, __bf16, _Float16>::type E;
     typedef typename V8<E>::t e8;
     typedef typename V8<E>::q e4;
@@ -296,6 +302,8 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
     typedef typename V8<E>::t e8;
     typedef typename V8<E>::q e4;
     constexpr int R = 32;
+    const int ntiles = th_live_tiles(a);
+    if ((int)blockIdx.x >= ntiles) return;               // block-uniform, before the first barrier (also: no live row at all)
     constexpr int KD = KS * 16;
     constexpr int P = KD * 2 + TH_PAD_FWD;
     constexpr int PLANE = R * P, BUF = 2 * PLANE;
@@ -325,7 +333,6 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
     const float4 bias4 = a.bias != nullptr ? ld4(a.bias + colb) : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool relu = a.epi == HOS_EPI_RELU;
 
-    const int ntiles = a.M / R;
     const int G = gridDim.x;
     float4 ra[AU], rb[PF2 ? AU : 1];
     // this thread's float4 units of a tile: unit u = t + 512 i -> (row, 16-byte column group)
@@ -353,7 +360,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
         }
     };
 
-    int tile = blockIdx.x;                               // grid <= ntiles
+    int tile = blockIdx.x;                               // < ntiles (workgroups past the live tiles have left)
     gload(ra, tile);
     sstore(ra, 0);
     gload(ra, tile + G);
@@ -450,6 +457,8 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
     typedef typename V8<E>::t e8;
     typedef typename V8<E>::q e4;
     constexpr int KS = 16, R = 32;
+    const int ntiles = th_live_tiles(a);
+    if ((int)blockIdx.x >= ntiles) return;               // block-uniform, before the first barrier
     constexpr int KD = KS * 16;
     constexpr int P = KD * 2 + th_pad<true>();
     constexpr int PLANE = R * P, BUF = 2 * PLANE;
@@ -474,7 +483,6 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
             for (int q = 0; q < 8; ++q) { E h, l; split_pair<E>(wcol[(size_t)(16 * s + q) * a.ldw], h, l); bh[s][q] = h; bl[s][q] = l; }
     }
     const int q4 = l31 & 3, colb = col0 + (l31 & ~3);
-    const int ntiles = a.M / R;
     const int G = gridDim.x;
     float4 ra[AU], rb[AU];
     uint32_t ba = 0, bb = 0, bits_staged = 0;
@@ -707,20 +715,23 @@ extern "C" int hos_canonical_fold_unfold(const float* gW0f, const float* db0, co
 // Y[M, N] = epi(X[M, :K] . W[:N, :K]^T + bias), N <= 256, K <= 320 (K % 4 == 0), epilogue HOS_EPI_NONE or HOS_EPI_RELU.
 // relu_bits (optional, 2 * 512 * ceil(M / 32) bytes): one bit per output element = "came out > 0", in the order the backward
 // kernel (hos_thin_linear_dgrad, mask_bits) consumes it; a waves's 32 columns that lie at or beyond N are not written.
-extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
-                                   int M, int N, int K, int epilogue, void* relu_bits, hos_stream_t stream) {
+// rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows are live -- read, computed and written;
+// the rest of X / Y / relu_bits is not touched.  *rows_dev is a multiple of 32 by contract (stage 3: n_live_rays * 128; M:1547-1551).
+extern "C" int hos_thin_linear_fwd_rows(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
+                                        int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream) {
     if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
     if (N > 256 || K > 320 || (epilogue != HOS_EPI_NONE && epilogue != HOS_EPI_RELU)) return HOS_E_SHAPE;
     if ((ldx & 3) || (ldw & 3) || (K & 3) || (((uintptr_t)X | (uintptr_t)W) & 15u)) return HOS_E_ALIGN;
     if (relu_bits && ((uintptr_t)relu_bits & 1u)) return HOS_E_ALIGN;
-    ThinArgs a{X, ldx, W, ldw, bias, Y, ldy, M, N, K, epilogue, nullptr, 0, hos_range_flag_ptr(), static_cast<uint16_t*>(relu_bits)};
+    ThinArgs a{X, ldx, W, ldw, bias, Y, ldy, M, N, K, epilogue, nullptr, 0, hos_range_flag_ptr(), static_cast<uint16_t*>(relu_bits), rows_dev};
     hipStream_t s = static_cast<hipStream_t>(stream);
     // reduction steps held in registers: 4 (the folded canonical input layer, 64 columns), 8, 16, 20 (the folded skip layer:
     // [fourier 64 | h 256]; 250 VGPRs -- 24 steps for the reference-shaped 384-wide concat row do not fit two waves per SIMD)
     // whole tiles of the shapes the canonical MLP runs (256 outputs; 64 / 256 / 320 inputs): the unpredicated kernel; a ragged
     // tail of M % 32 rows goes through the generic one
+    // (with a device-side bound only whole-tile capacities: the ragged tail's launch would need the bound minus its offset)
     if (N == 256 && M >= 32 && (K == 64 || K == 256 || K == 320) && !(ldy & 3) && !((uintptr_t)Y & 15u) &&
-        (!bias || !((uintptr_t)bias & 15u)) && !((uintptr_t)relu_bits & 3u)) {
+        (!bias || !((uintptr_t)bias & 15u)) && !((uintptr_t)relu_bits & 3u) && (!rows_dev || !(M & 31))) {
         ThinArgs f = a;
         f.M = M & ~31;
         int rc;
@@ -735,24 +746,32 @@ extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int 
     return K <= 256 ? launch_thin<16, false>(a, s) : launch_thin<20, false>(a, s);
 }
 
+extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
+                                   int M, int N, int K, int epilogue, void* relu_bits, hos_stream_t stream) {
+    return hos_thin_linear_fwd_rows(X, ldx, W, ldw, bias, Y, ldy, M, N, K, epilogue, relu_bits, nullptr, stream);
+}
+
 // dX[M, K] = (dY[M, :Npad] . W[:Npad, :K]) * [mask > 0], K <= 256 output columns, Npad <= 256 (Npad % 4 == 0; rows of W and
 // columns of dY beyond the layer's width are zero by contract).  mask: the layer's input activations [M, >= K] or NULL;
 // W and mask may start at ANY column of their matrices (4-byte aligned: the h part of a skip layer's concat row starts at
 // column 127; the mask's 16-byte groups around the window must be readable), dY and dX rows are 16-byte aligned.
 // mask_bits (optional): the bit mask hos_thin_linear_fwd wrote for the layer's input activations (its Y [M, K]); takes
 // precedence over `mask` and removes the re-read of the fp32 activations (a third of this kernel's HBM traffic).
-extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
-                                     const void* mask_bits, float* dX, int lddx, int M, int K, hos_stream_t stream) {
+// rows_dev: as hos_thin_linear_fwd_rows (rows of dY, mask, mask_bits and dX at and behind the bound are not touched).
+extern "C" int hos_thin_linear_dgrad_rows(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
+                                          const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev,
+                                          hos_stream_t stream) {
     if (!dY || !W || !dX || M <= 0 || K <= 0 || Npad <= 0) return HOS_E_ARG;
     if (K > 256 || Npad > 256) return HOS_E_SHAPE;
     if ((lddy & 3) || (Npad & 3) || (mask && (ldmask & 3)) || ((uintptr_t)dY & 15u) || (((uintptr_t)W | (uintptr_t)mask) & 3u)) return HOS_E_ALIGN;
     if (mask_bits && ((uintptr_t)mask_bits & 1u)) return HOS_E_ALIGN;
     ThinArgs a{dY, lddy, W, ldw, nullptr, dX, lddx, M, K, Npad, 0, mask_bits ? nullptr : mask, ldmask, nullptr,
-               static_cast<uint16_t*>(const_cast<void*>(mask_bits))};
+               static_cast<uint16_t*>(const_cast<void*>(mask_bits)), rows_dev};
     hipStream_t s = static_cast<hipStream_t>(stream);
     // whole tiles of a full 256 x 256 layer (or its 64-column Fourier window) with the bit mask or no mask: the unpredicated kernel;
     // ragged tail: generic
-    if ((K == 256 || K == 64) && Npad == 256 && M >= 32 && (mask_bits || !mask) && !(lddx & 3) && !((uintptr_t)dX & 15u)) {
+    if ((K == 256 || K == 64) && Npad == 256 && M >= 32 && (mask_bits || !mask) && !(lddx & 3) && !((uintptr_t)dX & 15u) &&
+        (!rows_dev || !(M & 31))) {
         ThinArgs f = a;
         f.M = M & ~31;
         const int rc = mask_bits ? launch_thin_dgrad_fast<true>(f, s) : launch_thin_dgrad_fast<false>(f, s);
@@ -761,4 +780,9 @@ extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, 
         if (a.bits) a.bits += (size_t)(f.M / 32) * TH_NT;
     }
     return Npad <= 128 ? launch_thin<8, true>(a, s) : launch_thin<16, true>(a, s);
+}
+
+extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
+                                     const void* mask_bits, float* dX, int lddx, int M, int K, hos_stream_t stream) {
+    return hos_thin_linear_dgrad_rows(dY, lddy, W, ldw, Npad, mask, ldmask, mask_bits, dX, lddx, M, K, nullptr, stream);
 }

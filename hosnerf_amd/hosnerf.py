@@ -87,11 +87,13 @@ class HOSNeRF(nn.Module):
                      "radii": batch["radii"], "times": batch["time"]}
         # the reference passes train_frac = 1.0 and randomized = True everywhere in stage 3 (M:1512-1516, M:720-723)
         dev = batch["rays_o_bkg"].device
+        # training steps run the human branch behind the warp on the foreground rays only (ops.LIVE_RAYS; M:1547-1551)
+        live = bool(ops.LIVE_RAYS and is_train and torch.is_grad_enabled())
         if self.two_streams and dev.type == "cuda":
             cur, side = torch.cuda.current_stream(dev), self.side_stream(dev)
             side.wait_stream(cur)                                  # fork: everything queued so far (inputs, last step's Adam) is visible
             with torch.cuda.stream(side):
-                out = self.human(t_rand=t_rand, prologue=prologue, with_cycle=with_cycle, static_cycle=static_cycle, **batch)
+                out = self.human(t_rand=t_rand, prologue=prologue, with_cycle=with_cycle, static_cycle=static_cycle, live_rays=live, **batch)
             _, hist = self.model(batch_bkg, 1.0, randomized, is_train, self.near_bkg, self.far_bkg, jitters=jitters)
             cur.wait_stream(side)                                  # join before the z-merge
             # The human outputs were allocated on the side stream and are consumed on this one (z-merge, losses, and -- as saved
@@ -105,7 +107,7 @@ class HOSNeRF(nn.Module):
                 out["human_rgbsigma"] = _JoinAfterBackward.apply(out["human_rgbsigma"], self)
         else:
             _, hist = self.model(batch_bkg, 1.0, randomized, is_train, self.near_bkg, self.far_bkg, jitters=jitters)
-            out = self.human(t_rand=t_rand, prologue=prologue, with_cycle=with_cycle, static_cycle=static_cycle, **batch)
+            out = self.human(t_rand=t_rand, prologue=prologue, with_cycle=with_cycle, static_cycle=static_cycle, live_rays=live, **batch)
         last = hist[-1]
         if maps:
             m = ops.merge_composite_maps(

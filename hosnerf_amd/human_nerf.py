@@ -564,8 +564,10 @@ class Network(FlatModule):
         ops.linear_fwd(h, 128, Wt, bt, 3, xyz, ops.EPI_RESIDUAL, aux=x, rows_dev=rows_dev)
         return xyz, ((E, PE, acts, None) if save else None)
 
-    def _canonical_fwd(self, cnl: torch.Tensor, state: int, save: bool):
-        """mlp_rgb_sigma.py:49-58 + N:539-540: [P,4] = (sigmoid rgb, relu sigma)."""
+    def _canonical_fwd(self, cnl: torch.Tensor, state: int, save: bool, rows_dev=None):
+        """mlp_rgb_sigma.py:49-58 + N:539-540: [P,4] = (sigmoid rgb, relu sigma).
+        `rows_dev` (int32 [1] on the device): only that many leading rows are live (the foreground rays of a stage-3 step); rows
+        behind them are left as they are in every buffer, `raw` included.  Thin-kernel row counts only (ops.thin_dgrad_rows)."""
         Pn = cnl.shape[0]
         dev = cnl.device
         embed = self._embeds.view(self.store.param)[state]
@@ -574,6 +576,8 @@ class Network(FlatModule):
         # concat rows [fourier 63 | 0 | h 256] with the h part 16-byte aligned -- 64 / 320 columns instead of 128 / 384, and the
         # 320-wide skip layer fits the register-resident thin kernel (20 reduction steps) instead of the tiled GEMM.
         fold = None
+        if rows_dev is not None and not ops.thin_dgrad_rows(Pn):
+            raise ValueError("_canonical_fwd(rows_dev=...): the row bound exists on the thin-kernel path only (ops.thin_dgrad_rows)")
         if ops.CNL_FOLD and ops.thin_dgrad_rows(Pn):
             fkey = ("cnl_fold",) + ops._stream_key(dev)       # per (device, stream): packed with this call's embedding, read by its backward
             fb = self._chain_bufs.get(fkey)
@@ -584,13 +588,13 @@ class Network(FlatModule):
             ops.canonical_fold_pack(W0, b0, W5, b5, embed, 256, CNL_NF, 256, fw)
             E = torch.empty(Pn, CNL_NFP, device=dev)
             CAT = torch.empty(Pn, CNL_NFP + 256, device=dev)
-            ops.embed_fourier(cnl, 10, ops.zero1(dev), E, CAT)          # a one-element zero "state" = the pad column of both rows
+            ops.embed_fourier(cnl, 10, ops.zero1(dev), E, CAT, rows_dev=rows_dev)   # a one-element zero "state" = the pad column of both rows
             fold = (fw, embed)
         else:
             E = torch.empty(Pn, CNL_LDE, device=dev)
             CAT = torch.empty(Pn, CNL_CAT, device=dev)
             CAT[:, CNL_CAT - 1].zero_()
-            ops.embed_fourier(cnl, 10, embed, E, CAT)
+            ops.embed_fourier(cnl, 10, embed, E, CAT, rows_dev=rows_dev)
         acts, bits = [], []
         h = E
         # training: every layer on the thin kernel also writes its ReLU mask as one bit per element (1 KB per 32 rows), which the
@@ -605,18 +609,19 @@ class Network(FlatModule):
                 K = Wt.shape[1]
             rb = ops.thin_relu_bits(Pn, dev) if (want_bits and K <= 320) else None
             if i == 4:      # its output feeds the skip concat: write it behind the input columns of CAT
-                ops.linear_fwd(h, K, Wt, bt, 256, CAT, ops.EPI_RELU, out_col0=CNL_NFP if fold is not None else 127, relu_bits=rb)
+                ops.linear_fwd(h, K, Wt, bt, 256, CAT, ops.EPI_RELU, out_col0=CNL_NFP if fold is not None else 127, relu_bits=rb,
+                               rows_dev=rows_dev)
                 acts.append(CAT)
                 h = CAT
             else:
                 out = torch.empty(Pn, 256, device=dev)
-                ops.linear_fwd(h, K, Wt, bt, 256, out, ops.EPI_RELU, relu_bits=rb)
+                ops.linear_fwd(h, K, Wt, bt, 256, out, ops.EPI_RELU, relu_bits=rb, rows_dev=rows_dev)
                 acts.append(out)
                 h = out
             bits.append(rb)
         Wt, bt = self._w(self._cnl[8])
         raw = torch.empty(Pn, 4, device=dev)
-        ops.linear_fwd(h, 256, Wt, bt, 4, raw, ops.EPI_SIGMOID_RELU4)
+        ops.linear_fwd(h, 256, Wt, bt, 4, raw, ops.EPI_SIGMOID_RELU4, rows_dev=rows_dev)
         return raw, ((E, acts, bits, fold) if save else None)
 
     # ------------------------------------------------------------------ HIP MLP chains (backward)
@@ -688,17 +693,19 @@ class Network(FlatModule):
             return ops.embed_bwd_res(x, band_w, band_w.numel(), False, dE, 0, dPE, 0, res, rows_dev=rows_dev)
         return ops.embed_bwd_res(x, band_w, band_w.numel(), False, dE, 75, dPE, 0, res, rows_dev=rows_dev)
 
-    def _canonical_bwd(self, saved, cnl: torch.Tensor, raw: torch.Tensor, g_raw: torch.Tensor, state: int):
+    def _canonical_bwd(self, saved, cnl: torch.Tensor, raw: torch.Tensor, g_raw: torch.Tensor, state: int, rows_dev=None):
+        """`rows_dev`: the bound of the forward; rows of the returned [P,3] behind it are not written."""
         E, acts, bits, fold = saved
+        rd = rows_dev
         CAT = acts[4]
         Pn, dev = cnl.shape[0], cnl.device
         dz8 = torch.empty(Pn, 32, device=dev)
-        ops.rgbsigma_grad(g_raw.contiguous(), raw, dz8)               # writes the whole zero-padded row
+        ops.rgbsigma_grad(g_raw.contiguous(), raw, dz8, rows_dev=rd)  # writes the whole zero-padded row
         Wt, _ = self._w(self._cnl[8])
         gW, gb = self._w(self._cnl[8], grad=True)
-        ops.linear_wgrad(dz8, acts[7], gW, gb, 4, 256)
+        ops.linear_wgrad(dz8, acts[7], gW, gb, 4, 256, rows_dev=rd)
         dz = torch.empty(Pn, 256, device=dev)
-        ops.linear_dgrad(dz8, Wt, 32, 256, dz, mask_src=acts[7], mask_bits=bits[7])
+        ops.linear_dgrad(dz8, Wt, 32, 256, dz, mask_src=acts[7], mask_bits=bits[7], rows_dev=rd)
         dCAT = dE = None
         tmp_b = {}
         if fold is not None:
@@ -712,42 +719,42 @@ class Network(FlatModule):
                 gW, gb = self._w(L, grad=True)
                 if i == 5 and fold is not None:
                     W5f = fold[0][2]
-                    ops.linear_wgrad(dz, CAT, gfold[2], gfold[3], 256, CNL_NFP + 256)
+                    ops.linear_wgrad(dz, CAT, gfold[2], gfold[3], 256, CNL_NFP + 256, rows_dev=rd)
                     nxt = torch.empty(Pn, 256, device=dev)
                     dCAT = torch.empty(Pn, CNL_NFP, device=dev)
-                    ops.linear_dgrad(dz, W5f, 256, CNL_NFP, dCAT, thin=True)
-                    ops.linear_dgrad(dz, W5f, 256, 256, nxt, mask_src=CAT, w_col0=CNL_NFP, mask_col0=CNL_NFP, mask_bits=bits[4])
+                    ops.linear_dgrad(dz, W5f, 256, CNL_NFP, dCAT, thin=True, rows_dev=rd)
+                    ops.linear_dgrad(dz, W5f, 256, 256, nxt, mask_src=CAT, w_col0=CNL_NFP, mask_col0=CNL_NFP, mask_bits=bits[4], rows_dev=rd)
                     dz = nxt
                 elif i == 0 and fold is not None:
-                    ops.linear_wgrad(dz, E, gfold[0], gfold[1], 256, CNL_NFP)
+                    ops.linear_wgrad(dz, E, gfold[0], gfold[1], 256, CNL_NFP, rows_dev=rd)
                     dE = torch.empty(Pn, CNL_NFP, device=dev)
-                    ops.linear_dgrad(dz, fold[0][0], 256, CNL_NFP, dE, thin=True)
+                    ops.linear_dgrad(dz, fold[0][0], 256, CNL_NFP, dE, thin=True, rows_dev=rd)
                 elif i == 5:
                     tmp_b[5] = ops.zeros(L.Npad, dev)
-                    ops.linear_wgrad(dz, CAT, gW, tmp_b[5], 256, CNL_CAT)
+                    ops.linear_wgrad(dz, CAT, gW, tmp_b[5], 256, CNL_CAT, rows_dev=rd)
                     nxt = torch.empty(Pn, 256, device=dev)
                     if ops.thin_dgrad_rows(Pn):
                         # the two consumers of d(concat row) take their own column windows straight from the weight: the
                         # Fourier part (63 columns; the state embedding's gradient goes through db below) and the h part
                         # (columns 127..382, through layer 4's ReLU) -- no [P, 384] round trip, no slice + mask pass
                         dCAT = torch.empty(Pn, 64, device=dev)
-                        ops.linear_dgrad(dz, Wt, 256, 64, dCAT, thin=True)
-                        ops.linear_dgrad(dz, Wt, 256, 256, nxt, mask_src=CAT, w_col0=127, mask_col0=127, mask_bits=bits[4])
+                        ops.linear_dgrad(dz, Wt, 256, 64, dCAT, thin=True, rows_dev=rd)
+                        ops.linear_dgrad(dz, Wt, 256, 256, nxt, mask_src=CAT, w_col0=127, mask_col0=127, mask_bits=bits[4], rows_dev=rd)
                     else:
                         dCAT = torch.empty(Pn, CNL_CAT, device=dev)
-                        ops.linear_dgrad(dz, Wt, 256, CNL_CAT, dCAT)
-                        ops.slice_mask(dCAT, 127, CAT, 127, 256, nxt)             # h-part of the concat, through layer 4's ReLU
+                        ops.linear_dgrad(dz, Wt, 256, CNL_CAT, dCAT, rows_dev=rd)
+                        ops.slice_mask(dCAT, 127, CAT, 127, 256, nxt, rows_dev=rd)             # h-part of the concat, through layer 4's ReLU
                     dz = nxt
                 elif i == 0:
                     tmp_b[0] = ops.zeros(L.Npad, dev)
-                    ops.linear_wgrad(dz, E, gW, tmp_b[0], 256, CNL_LDE)
+                    ops.linear_wgrad(dz, E, gW, tmp_b[0], 256, CNL_LDE, rows_dev=rd)
                     dE = torch.empty(Pn, CNL_LDE, device=dev)
-                    ops.linear_dgrad(dz, Wt, 256, CNL_LDE, dE)
+                    ops.linear_dgrad(dz, Wt, 256, CNL_LDE, dE, rows_dev=rd)
                 else:
                     inp = acts[i - 1]
-                    ops.linear_wgrad(dz, inp, gW, gb, 256, 256)
+                    ops.linear_wgrad(dz, inp, gW, gb, 256, 256, rows_dev=rd)
                     nxt = torch.empty(Pn, 256, device=dev)
-                    ops.linear_dgrad(dz, Wt, 256, 256, nxt, mask_src=inp, mask_bits=bits[i - 1])
+                    ops.linear_dgrad(dz, Wt, 256, 256, nxt, mask_src=inp, mask_bits=bits[i - 1], rows_dev=rd)
                     dz = nxt
         g_embed = self._embeds.view(self.store.grad)[state]
         if fold is not None:
@@ -762,7 +769,7 @@ class Network(FlatModule):
                 gb += tmp_b[i]
                 g_embed.addmv_(Wt[:256, 63:127].t(), tmp_b[i][:256])
         g_cnl = torch.empty(Pn, 3, device=dev)
-        ops.embed_bwd(cnl, None, 10, True, dE, 0, dCAT, 0, g_cnl, False)
+        ops.embed_bwd(cnl, None, 10, True, dE, 0, dCAT, 0, g_cnl, False, rows_dev=rd)
         return g_cnl
 
     # ------------------------------------------------------------------ reference-style forward
@@ -822,18 +829,22 @@ class Network(FlatModule):
         return pro
 
     def forward(self, rays, dst_Rs=None, dst_Ts=None, cnl_gtfms=None, motion_weights_priors=None, dst_posevec=None, near=None,
-                far=None, iter_val=1e7, t_rand=None, prologue=None, with_cycle: bool = True, static_cycle: bool = False, **kwargs):
+                far=None, iter_val=1e7, t_rand=None, prologue=None, with_cycle: bool = True, static_cycle: bool = False,
+                live_rays: bool = False, **kwargs):
         """Reference signature + keyword-only extensions: `t_rand` (the stratified jitter draws), `prologue` (a cached
         `frame_prologue`), `with_cycle=False` (evaluation loops never read the cycle outputs), `static_cycle=True`
         (fixed-shape cycle outputs [P,3] + `cycle_count` on the device instead of the reference's data-dependent
-        [n_selected,3]: no host synchronisation, the step can be captured in a hipGraph).
+        [n_selected,3]: no host synchronisation, the step can be captured in a hipGraph), `live_rays=True` (stage-3 training:
+        everything behind the backward warp runs on the foreground rays only, see `_forward`; `human_rgbsigma` and
+        `deform_pts_prev_final` of the other rays -- which the z-merge and the losses never read -- are zero).
         `self.gemm_mode` (None = process default) selects the arithmetic of this module's GEMMs (see ops.guarded_forward)."""
         return ops.guarded_forward(self, rays.device, lambda: self._forward(
             rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec, near, far, iter_val, t_rand, prologue, with_cycle,
-            static_cycle, **kwargs))
+            static_cycle, live_rays, **kwargs))
 
     def _forward(self, rays, dst_Rs=None, dst_Ts=None, cnl_gtfms=None, motion_weights_priors=None, dst_posevec=None, near=None,
-                 far=None, iter_val=1e7, t_rand=None, prologue=None, with_cycle: bool = True, static_cycle: bool = False, **kwargs):
+                 far=None, iter_val=1e7, t_rand=None, prologue=None, with_cycle: bool = True, static_cycle: bool = False,
+                 live_rays: bool = False, **kwargs):
         cfg = self.cfg
         dev = rays.device
         K = cfg.total_bones
@@ -854,11 +865,29 @@ class Network(FlatModule):
             t_rand = torch.rand(B, N, device=dev)                                  # N:421
         outs: Dict[str, List[torch.Tensor]] = {}
         chunk = int(cfg.chunk)
+        # Live rays (M:1547-1551): stage 3 with gradients, the whole batch in one chunk, at row counts where the
+        # canonical MLP runs on the thin kernels (the only ones that take a device-side row bound); ignored otherwise.
+        live_rays = bool(live_rays and self.stage == 3 and B <= chunk and torch.is_grad_enabled() and ops.thin_dgrad_rows(B * N))
         for c0 in range(0, B, chunk):
             sl = slice(c0, min(B, c0 + chunk))
             tr = None if t_rand is None else t_rand[sl].contiguous()
             grad = torch.is_grad_enabled()
-            if grad:
+            live = rows_live = None
+            if live_rays:
+                # the warp runs on all rays (its mask IS the selection); behind it the foreground rays' rows are packed to the
+                # front of fixed-capacity buffers and every kernel stops at `rows_live` (device memory: nothing is read on the host)
+                z, pts, x_skel, mask = ops.human_sample_warp_ad(vol, R_b, T_b, rays_o[sl], rays_d[sl], near[sl].contiguous(),
+                                                                far[sl].contiguous(), N, bmin, bscale, tr, K)
+                live = ops.select_live_rays(mask.detach().view(-1, N))
+                rows_live = live.rows
+                x_c = ops.gather_rays(x_skel.reshape(-1, 3), live)
+                mask_c = ops.gather_rays(mask.detach().reshape(-1, 1), live).view(-1)
+                pts_c = ops.gather_rays(pts.detach().reshape(-1, 3), live)
+                cnl = _NonRigidFn.apply(self._token, self, "nr", x_c, cond, band_w, rows_live)
+                n_use = 1 + int(flow) + int(with_cycle)
+                cnl_uses = list(ops.fanout(cnl, n_use))
+                raw = ops.scatter_rays(_CanonicalFn.apply(self._token, self, cnl_uses.pop(), state, rows_live), live)
+            elif grad:
                 z, pts, x_skel, mask = ops.human_sample_warp_ad(vol, R_b, T_b, rays_o[sl], rays_d[sl], near[sl].contiguous(),
                                                                 far[sl].contiguous(), N, bmin, bscale, tr, K)
                 cnl = _NonRigidFn.apply(self._token, self, "nr", x_skel, cond, band_w, None)
@@ -891,24 +920,32 @@ class Network(FlatModule):
                 d_ = ops.lbs_forward(c_pts, Rf_, Tf_, vol_cl, bmin, bscale, K, rows_dev=rows_dev)
                 return self._nonrigid_fwd(self._nrf, d_, cond_, band_w, save=False, rows_dev=rows_dev)[0]
 
-            if flow:                                                               # N:474-502
+            if flow and live is not None:
+                ret["deform_pts_prev_final"] = ops.scatter_rays(fwd_branch(cnl_uses.pop(), R_fp, T_fp, cond_prev, rows_dev=rows_live),
+                                                                live).view(b, N, 3)
+            elif flow:                                                             # N:474-502
                 ret["deform_pts_prev_final"] = fwd_branch(cnl_uses.pop(), R_fp, T_fp, cond_prev).view(b, N, 3)
             # N:505-536 (data-dependent size); the frame loops of eval.py never read the cycle outputs and switch them off
+            # (live rays: the packed copies -- the tail of mask_c is zero, so no dead row is selected; content and order of the
+            # set are those of the full-size selection)
+            cyc_mask, cyc_pts = (mask_c, pts_c) if live is not None else (mask, pts)
             if with_cycle and static_cycle:
                 # fixed-capacity form for captured training steps: the selection is a device-side compaction, the row count
                 # stays in device memory (`cycle_count`), rows past it are zero and receive zero gradients
                 if B > chunk:
                     raise ValueError("static_cycle needs the whole ray batch in one chunk (cfg.chunk >= number of rays)")
-                sel_cnl, observe, _, count = ops.compact_rows(mask, 0.005, cnl_uses.pop(), pts)
+                sel_cnl, observe, _, count = ops.compact_rows(cyc_mask, 0.005, cnl_uses.pop(), cyc_pts)
                 # the kernels stop at `count` rows
                 ret["deform_pts_final"] = fwd_branch(sel_cnl, R_f, T_f, cond, rows_dev=count)
                 ret["observe_pts"] = observe
                 ret["cycle_count"] = count
+                if live is not None:
+                    ret["live_ray_rows"] = rows_live
             elif with_cycle:
-                sel = torch.nonzero(mask.detach() > 0.005).reshape(-1)
+                sel = torch.nonzero(cyc_mask.detach().reshape(-1) > 0.005).reshape(-1)
                 if sel.numel() > 0:
                     ret["deform_pts_final"] = fwd_branch(cnl_uses.pop().index_select(0, sel), R_f, T_f, cond)
-                    ret["observe_pts"] = pts.view(-1, 3).index_select(0, sel)
+                    ret["observe_pts"] = cyc_pts.view(-1, 3).index_select(0, sel)
                 else:
                     ret["deform_pts_final"] = pts[0, 0][None]
                     ret["observe_pts"] = pts[0, 0][None]
@@ -945,16 +982,16 @@ class _NonRigidFn(torch.autograd.Function):
 
 class _CanonicalFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, token, net: Network, cnl, state):
+    def forward(ctx, token, net: Network, cnl, state, rows_dev=None):
         cnl = cnl.contiguous()
-        raw, saved = net._canonical_fwd(cnl, state, save=True)
-        ctx.net, ctx.saved, ctx.cnl, ctx.raw, ctx.state = net, saved, cnl, raw, state
+        raw, saved = net._canonical_fwd(cnl, state, save=True, rows_dev=rows_dev)
+        ctx.net, ctx.saved, ctx.cnl, ctx.raw, ctx.state, ctx.rows_dev = net, saved, cnl, raw, state, rows_dev
         ctx.mode = ops.get_gemm_mode()
         return raw
 
     @staticmethod
     def backward(ctx, g):
         with ops.gemm_mode(ctx.mode):
-            g_cnl = ctx.net._canonical_bwd(ctx.saved, ctx.cnl, ctx.raw, g.contiguous(), ctx.state)
+            g_cnl = ctx.net._canonical_bwd(ctx.saved, ctx.cnl, ctx.raw, g.contiguous(), ctx.state, rows_dev=ctx.rows_dev)
         ctx.saved = ctx.raw = None                       # break the output -> grad_fn -> ctx -> output cycle right away
-        return None, None, g_cnl, None
+        return None, None, g_cnl, None, None

@@ -111,12 +111,12 @@ def linear_fwd(A0: torch.Tensor, K0: int, W: torch.Tensor, bias: Optional[torch.
     M = A0.shape[0] if M is None else M
     if epilogue == EPI_RESIDUAL:
         aux_col = aux.stride(0)
-    if (rows_dev is None and A1 is None and 128 < N <= 256 and K0 <= 320 and K0 % 4 == 0 and M >= 16384 and epilogue in (EPI_NONE, EPI_RELU)
+    if (A1 is None and 128 < N <= 256 and K0 <= 320 and K0 % 4 == 0 and M >= 16384 and epilogue in (EPI_NONE, EPI_RELU)
             and ldc is None and out is not None and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3):
         # many rows through a thin layer: persistent kernel with the weight in registers (hos_thin.hip)
         _timed(f"thin_fwd[M={M},N={N},K={K0}]", 2.0 * M * N * K0, lambda: call(
-            "hos_thin_linear_fwd", ptr(A0), A0.stride(0), ptr(W), W.stride(0), ptr(bias), ptr(out) + 4 * out_col0, out.stride(0),
-            M, N, K0, epilogue, ptr(relu_bits, torch.int16)))
+            "hos_thin_linear_fwd_rows", ptr(A0), A0.stride(0), ptr(W), W.stride(0), ptr(bias), ptr(out) + 4 * out_col0, out.stride(0),
+            M, N, K0, epilogue, ptr(relu_bits, torch.int16), ptr(rows_dev, torch.int32)))
         return out
     if relu_bits is not None:
         raise _lib.HosLibraryError("relu_bits: this layer does not run on the thin kernel (check ops.thin_dgrad_rows first)")
@@ -129,6 +129,10 @@ def linear_fwd(A0: torch.Tensor, K0: int, W: torch.Tensor, bias: Optional[torch.
 
 # the canonical MLP with its per-call state embedding folded into the biases of the input layer and the skip layer (hos_thin.hip)
 CNL_FOLD = True
+# Stage-3 training: everything behind the backward warp (non-rigid chains, canonical MLP, flow set, cycle set) runs on the
+# foreground rays only -- the z-merge never reads the human samples of a ray whose mask sum is <= 5e-3 (M:1547-1551; DESIGN
+# section 4).  False: all rays, as the reference computes them (the tests' reference path).
+LIVE_RAYS = True
 _CNL_FOLD_WS = {}
 _ZERO1 = {}
 
@@ -262,11 +266,12 @@ def thin_relu_bits(M: int, device) -> torch.Tensor:
 
 def linear_dgrad(dY: torch.Tensor, W: torch.Tensor, Npad: int, K: int, out: torch.Tensor,
                  mask_src: Optional[torch.Tensor] = None, accumulate: bool = False, w_col0: int = 0, mask_col0: int = 0,
-                 thin: bool = False, mask_bits: Optional[torch.Tensor] = None):
+                 thin: bool = False, mask_bits: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None):
     """out[M, :K] = (dY[:, :Npad] @ W[:Npad, w_col0:w_col0+K]) * (mask_src[:, mask_col0:mask_col0+K] > 0).
     `thin`: take the thin kernel also for K <= 128 output columns (by default those go to the tiled GEMM).
     `mask_bits`: the bit mask `linear_fwd(relu_bits=...)` wrote for the K <= 256 columns of this layer's input (thin kernel only);
-    used instead of `mask_src`."""
+    used instead of `mask_src`.
+    `rows_dev` (int32 [1] on the device): only that many leading rows are live (thin kernel only)."""
     M = dY.shape[0]
     wptr = ptr(W) + 4 * w_col0
     mptr = None if mask_src is None else ptr(mask_src) + 4 * mask_col0
@@ -277,10 +282,12 @@ def linear_dgrad(dY: torch.Tensor, W: torch.Tensor, Npad: int, K: int, out: torc
         for k0 in range(0, K, 256):
             kc = min(256, K - k0)
             _timed(f"thin_dgrad[M={M},N={kc},K={Npad}]", 2.0 * M * kc * Npad, lambda: call(
-                "hos_thin_linear_dgrad", ptr(dY), dY.stride(0), wptr + 4 * k0, W.stride(0), Npad,
+                "hos_thin_linear_dgrad_rows", ptr(dY), dY.stride(0), wptr + 4 * k0, W.stride(0), Npad,
                 None if mptr is None else mptr + 4 * k0, 0 if mask_src is None else mask_src.stride(0), ptr(mask_bits, torch.int16),
-                ptr(out) + 4 * k0, out.stride(0), M, kc))
+                ptr(out) + 4 * k0, out.stride(0), M, kc, ptr(rows_dev, torch.int32)))
         return out
+    if rows_dev is not None:
+        raise _lib.HosLibraryError("rows_dev: this layer does not run on the thin kernel (check ops.thin_dgrad_rows first)")
     if mask_bits is not None and mask_src is None:
         raise _lib.HosLibraryError("mask_bits: this layer does not run on the thin kernel (check ops.thin_dgrad_rows first)")
     _timed(f"gemm_dgrad[M={M},N={K},K={Npad}]", 2.0 * M * K * Npad, lambda: call(
@@ -290,8 +297,9 @@ def linear_dgrad(dY: torch.Tensor, W: torch.Tensor, Npad: int, K: int, out: torc
 
 
 def linear_wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, db: Optional[torch.Tensor], N: int, K: int,
-                 w_col0: int = 0, splits: int = 0):
-    """dW[:N, w_col0:w_col0+K] += dY[:, :N]^T @ X[:, :K];  db[:N] += colsum(dY[:, :N])."""
+                 w_col0: int = 0, splits: int = 0, rows_dev: Optional[torch.Tensor] = None):
+    """dW[:N, w_col0:w_col0+K] += dY[:, :N]^T @ X[:, :K];  db[:N] += colsum(dY[:, :N]).
+    `rows_dev` (int32 [1] on the device): only that many leading rows enter the sums (the many-row thin kernel and N <= 32)."""
     M = dY.shape[0]
     if 128 < N <= 256 and M >= 16384 and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3:
         # many rows, thin layer: staged-planes kernel with transposed LDS reads (hos_mlpbwd.hip), K in chunks of <= 256
@@ -299,12 +307,12 @@ def linear_wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, db: Option
             kc = min(256, K - k0)
             ws = _bwd_workspace(dY.device, M, N, kc, False)
             _timed(f"wgrad_tr[M={N},N={kc},K={M}]", 2.0 * M * N * kc, lambda: call(
-                "hos_linear_wgrad_tr", ptr(dY), dY.stride(0), ptr(X) + 4 * k0, X.stride(0), ptr(dW) + 4 * (w_col0 + k0), dW.stride(0),
-                ptr(db) if k0 == 0 else None, M, N, kc, ptr(ws), ws.numel()))
+                "hos_linear_wgrad_tr_rows", ptr(dY), dY.stride(0), ptr(X) + 4 * k0, X.stride(0), ptr(dW) + 4 * (w_col0 + k0), dW.stride(0),
+                ptr(db) if k0 == 0 else None, M, N, kc, ptr(ws), ws.numel(), ptr(rows_dev, torch.int32)))
         return
     _timed(f"gemm_wgrad[M={N},N={K},K={M}]", 2.0 * M * N * K, lambda: call(
-        "hos_linear_wgrad", ptr(dY), dY.stride(0), ptr(X), X.stride(0), ptr(dW) + 4 * w_col0, dW.stride(0),
-        ptr(db), M, N, K, splits))
+        "hos_linear_wgrad_rows", ptr(dY), dY.stride(0), ptr(X), X.stride(0), ptr(dW) + 4 * w_col0, dW.stride(0),
+        ptr(db), M, N, K, splits, ptr(rows_dev, torch.int32)))
 
 
 def linear_bwd_fused(dY: torch.Tensor, X: torch.Tensor, W: torch.Tensor, dW: torch.Tensor, db: Optional[torch.Tensor], N: int,
@@ -1227,10 +1235,10 @@ def embed_hannw(x, band_w, cond, E, PE=None, rows_dev=None):
          ptr(E), E.stride(0), ptr(PE), 0 if PE is None else PE.stride(0), ptr(rows_dev, torch.int32))
 
 
-def embed_fourier(x, num_freqs, state, E, E2=None):
+def embed_fourier(x, num_freqs, state, E, E2=None, rows_dev=None):
     P = x.shape[0]
-    call("hos_embed_fourier", ptr(x), num_freqs, ptr(state), 0 if state is None else state.numel(), P,
-         ptr(E), E.stride(0), ptr(E2), 0 if E2 is None else E2.stride(0))
+    call("hos_embed_fourier_rows", ptr(x), num_freqs, ptr(state), 0 if state is None else state.numel(), P,
+         ptr(E), E.stride(0), ptr(E2), 0 if E2 is None else E2.stride(0), ptr(rows_dev, torch.int32))
 
 
 # ------------------------------------------------------------------------------------------ composites
@@ -1474,6 +1482,76 @@ def compact_rows(mask, thr: float, a, b):
     return _CompactRows.apply(mask.detach().reshape(-1).contiguous(), thr, a.reshape(-1, 3).contiguous(), b.detach().reshape(-1, 3).contiguous())
 
 
+# ------------------------------------------------------------------------------------------ live rays of a stage-3 step (M:1547-1551)
+class LiveRays:
+    """Selection of the foreground rays of a [B, S] mask (hos_select_live_rays): `ray_ids` int32 [B] (ascending, then -1), `flag`
+    int32 [B] (the z-merge's own decision, bit for bit) and `rows` int32 [1] = n_live * S, all on the device."""
+
+    def __init__(self, mask: torch.Tensor, thr: float = 5e-3):
+        B, S = mask.shape
+        dev = mask.device
+        self.B, self.S = B, S
+        self.ray_ids = torch.empty(B, dtype=torch.int32, device=dev)
+        self.flag = torch.empty(B, dtype=torch.int32, device=dev)
+        self.rows = torch.empty(1, dtype=torch.int32, device=dev)
+        call("hos_select_live_rays", ptr(mask.detach().contiguous()), float(thr), B, S, ptr(self.ray_ids, torch.int32),
+             ptr(self.flag, torch.int32), ptr(self.rows, torch.int32))
+
+
+def select_live_rays(mask: torch.Tensor, thr: float = 5e-3) -> LiveRays:
+    return LiveRays(mask, thr)
+
+
+def _gather_rays_raw(src: torch.Tensor, live: LiveRays) -> torch.Tensor:
+    src = src.contiguous()
+    C = src.numel() // (live.B * live.S)
+    dst = torch.empty(live.B * live.S, C, device=src.device)
+    call("hos_gather_rays", ptr(src), ptr(live.ray_ids, torch.int32), ptr(live.rows, torch.int32), live.B, live.S, C, ptr(dst))
+    return dst
+
+
+def _scatter_rays_raw(src: torch.Tensor, live: LiveRays) -> torch.Tensor:
+    src = src.contiguous()
+    C = src.numel() // (live.B * live.S)
+    dst = torch.empty(live.B * live.S, C, device=src.device)
+    call("hos_scatter_rays", ptr(src), ptr(live.ray_ids, torch.int32), ptr(live.flag, torch.int32), ptr(live.rows, torch.int32),
+         live.B, live.S, C, ptr(dst))
+    return dst
+
+
+class _GatherRays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, live):
+        ctx.live = live
+        return _gather_rays_raw(src, live)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _scatter_rays_raw(g, ctx.live), None
+
+
+class _ScatterRays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, live):
+        ctx.live = live
+        return _scatter_rays_raw(src, live)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _gather_rays_raw(g, ctx.live), None
+
+
+def gather_rays(src: torch.Tensor, live: LiveRays) -> torch.Tensor:
+    """[B*S, C] -> [B*S, C]: the S rows of every live ray at the front (ray order kept), rows from `live.rows` on zero.  Its
+    gradient is `scatter_rays`."""
+    return _GatherRays.apply(src, live) if (src.requires_grad and torch.is_grad_enabled()) else _gather_rays_raw(src, live)
+
+
+def scatter_rays(src: torch.Tensor, live: LiveRays) -> torch.Tensor:
+    """The inverse of `gather_rays`; rows of background rays are zero.  Its gradient is `gather_rays`."""
+    return _ScatterRays.apply(src, live) if (src.requires_grad and torch.is_grad_enabled()) else _scatter_rays_raw(src, live)
+
+
 # ------------------------------------------------------------------------------------------ training losses (C4)
 _LOSS_WS = {}
 
@@ -1698,8 +1776,8 @@ def slice_pad(src, col0, width, out, rows_dev=None):
     call("hos_slice_pad", ptr(src), src.stride(0), col0, src.shape[0], width, ptr(out), out.stride(0), ptr(rows_dev, torch.int32))
 
 
-def rgbsigma_grad(g, y, dz):
-    call("hos_rgbsigma_grad", ptr(g), ptr(y), y.shape[0], ptr(dz), dz.stride(0))
+def rgbsigma_grad(g, y, dz, rows_dev=None):
+    call("hos_rgbsigma_grad_rows", ptr(g), ptr(y), y.shape[0], ptr(dz), dz.stride(0), ptr(rows_dev, torch.int32))
 
 
 def adam_step_dyn(p, g, m, v, hyper, beta1, beta2, eps, grad_scale=1.0, sumsq_buf=None, max_norm=0.0):

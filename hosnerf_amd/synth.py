@@ -175,7 +175,7 @@ def _ray_bbox(o, d, bmin, bmax):
 
 
 def human_batch(num_rays: int = 2048, seed: int = 777, time: float = 0.5, is_train: bool = True,
-                iter_val: float = 3e5, pose_sigma: float = 0.2) -> Dict[str, torch.Tensor]:
+                iter_val: float = 3e5, pose_sigma: float = 0.2, aim_sigma: float = 0.25) -> Dict[str, torch.Tensor]:
     """SURVEY 8(d) configs 3/4 + Appendix B: one synthetic training item of the human-object branch
     (reference kwargs of Network.forward) plus the stage-3 extras (`*_bkg`, `radii`, similarity)."""
     rs = np.random.RandomState(seed)
@@ -209,7 +209,8 @@ def human_batch(num_rays: int = 2048, seed: int = 777, time: float = 0.5, is_tra
     pmin, pmax = posed.min(0) - 0.6, posed.max(0) + 0.6
 
     cam = np.array([0.3, 0.2, 3.0], np.float32)
-    tgt = posed[rs.randint(0, K, size=num_rays)] + (rs.standard_normal((num_rays, 3)) * 0.25).astype(np.float32)
+    # (aim_sigma: spread of the aim points around the joints; 0 = every ray through a joint, i.e. no ray beside the body)
+    tgt = posed[rs.randint(0, K, size=num_rays)] + (rs.standard_normal((num_rays, 3)) * aim_sigma).astype(np.float32)
     d = tgt - cam
     d = d / np.abs(d[:, 2:3])                           # pixel-style directions: |d_z| = 1, not unit length
     o = np.broadcast_to(cam, d.shape).copy()

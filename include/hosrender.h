@@ -116,6 +116,10 @@ int hos_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npa
  * atomics over `splits` partitions of M (splits <= 0: chosen by the library). */
 int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
                      float* db, int M, int N, int K, int splits, hos_stream_t stream);
+/* ... over a fixed-capacity buffer: only the first min(M, *rows_dev) rows enter the sums, the rest is not read (rows_dev: int32 [1]
+ * in device memory, NULL: all M).  Narrow layers only (N <= 32: the canonical head); HOS_E_SHAPE otherwise. */
+int hos_linear_wgrad_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
+                          float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Fused backward of one thin layer (N, K <= 128) over M rows -- replaces a hos_linear_wgrad + hos_linear_dgrad pair on the
  * same (dY, X): dX [M,K] = (dY . W) masked by X > 0 (relu_mask != 0; dX NULL: skip), dW [N,ldw] += dY^T . X, db [N] += column
@@ -144,6 +148,10 @@ long long hos_mlp_bwd_ws_floats(int M, int N, int K, int fused);
  * Reference: autograd of the 256-wide nn.Linear layers of CanonicalMLP, canonical_mlps/mlp_rgb_sigma.py:49-58. */
 int hos_linear_wgrad_tr(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db,
                         int M, int N, int K, float* ws, int64_t ws_floats, hos_stream_t stream);
+/* ... with a device-side row bound (see "Live rays" below): only the first min(M, *rows_dev) rows enter the sums and nothing behind
+ * them is read; grid, slabs and reduction are those of the capacity M.  *rows_dev is a multiple of 32. */
+int hos_linear_wgrad_tr_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db,
+                             int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Thin layers over very many rows with the weight slice of every wave resident in registers (hos_thin.hip): N, K <= 256
  * (forward: K <= 320, the folded skip layer below).
@@ -160,6 +168,13 @@ int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const 
                         int M, int N, int K, int epilogue, void* relu_bits, hos_stream_t stream);
 int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
                           const void* mask_bits, float* dX, int lddx, int M, int K, hos_stream_t stream);
+/* The same two launches over fixed-capacity buffers: rows_dev (int32 [1] in device memory, NULL: all M) bounds the live rows;
+ * rows at and behind min(M, *rows_dev) -- of X / dY, mask, the bit mask and the output -- are neither read nor written (they are
+ * uninitialised memory).  *rows_dev is a multiple of 32 (stage 3: live rays x 128 samples, see hos_select_live_rays). */
+int hos_thin_linear_fwd_rows(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
+                             int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream);
+int hos_thin_linear_dgrad_rows(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
+                               const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev, hos_stream_t stream);
 
 /* CanonicalMLP with the state embedding folded into biases.  The reference concatenates ONE state vector per call to every
  * point's Fourier features (core/nets/human_nerf/network.py:177-230 picks it by frame time and expands it over the points), so its columns of the input
@@ -455,6 +470,9 @@ int hos_embed_hannw(const float* x, const float* band_w, int num_freqs, const fl
  * (the skip-concat buffer of mlp_rgb_sigma.py:52-53). */
 int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
                       float* E, int lde, float* E2, int lde2, hos_stream_t stream);
+/* ... only the first min(P, *rows_dev) rows (rows_dev: int32 [1] in device memory, NULL: all P). */
+int hos_embed_fourier_rows(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
+                           float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Backward of hos_human_sample_warp w.r.t. the motion-weight volume (atomics into g_vol [K,V,V,V]) and the
  * backward motion basis (g_R [K,9], g_T [K,3], accumulated with atomics -- caller zeroes them):
@@ -488,6 +506,9 @@ int hos_slice_pad(const float* src, int lds, int col0, int64_t P, int width, flo
  * (columns 4.. zero; ldz % 4 == 0, 16-byte aligned pointers). */
 int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
                       hos_stream_t stream);
+/* ... only the first min(P, *rows_dev) rows (rows_dev: int32 [1] in device memory, NULL: all P). */
+int hos_rgbsigma_grad_rows(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
+                           const int32_t* rows_dev, hos_stream_t stream);
 
 /* NeRF-style composite `_raw2outputs` (M:73-99; S2 form N2:273-299 with the activations applied by
  * the MLP epilogue): dists = [dz..., last_dist]*|d|; alpha = (1-exp(-sigma*dists))*mask;
@@ -642,6 +663,25 @@ int hos_compact_rows(const float* mask, float thr, const float* src_a, const flo
                      int32_t* sel, float* out_a, float* out_b, int32_t* workspace, hos_stream_t stream);
 /* The gather's gradient: dst [P,3] = 0, then dst[sel[j]] = src[j] for j < *count. */
 int hos_scatter_rows(const float* src, const int32_t* sel, const int32_t* count, int64_t P, float* dst, hos_stream_t stream);
+
+/* Live rays of a stage-3 training step.  The z-merge calls a ray foreground only if sum_s pts_mask[ray, s] > thre_fg
+ * (3rd_Complete_HOSNeRF/src/model/mipnerf360/model.py:1547-1551); every other ray is composited from its 32 background samples
+ * alone, its human samples receive zero gradients, the flow term skips it and it holds no cycle point -- so nothing behind the
+ * backward warp has to run for it.  The reference computes those rays and throws them away.
+ *   hos_select_live_rays: flag [B] = the decision of hos_merge_composite_fwd, bit for bit (the two kernels call one device
+ *                         function: one wavefront per ray, lane-strided partial sums, the same reduction tree, the same `>`);
+ *                         ray_ids [B] = the foreground rays' indices ascending, then -1; *rows_live = n_live * S.
+ *   hos_gather_rays:      dst [B*S, C]: the S rows of every live ray at the front (row j = src row ray_ids[j / S] * S + j % S),
+ *                         rows at and behind *rows_live zero.
+ *   hos_scatter_rays:     the inverse (dst [B*S, C] from the front of src; rows of background rays zero).  Each is the other's
+ *                         gradient.  src and dst must not overlap.
+ * No host read, fixed shapes: the count stays in device memory and bounds the launches in between (the *_rows entry points). */
+int hos_select_live_rays(const float* mask, float thr, int B, int S, int32_t* ray_ids, int32_t* flag, int32_t* rows_live,
+                         hos_stream_t stream);
+int hos_gather_rays(const float* src, const int32_t* ray_ids, const int32_t* rows_live, int B, int S, int C, float* dst,
+                    hos_stream_t stream);
+int hos_scatter_rays(const float* src, const int32_t* ray_ids, const int32_t* flag, const int32_t* rows_live, int B, int S,
+                     int C, float* dst, hos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training losses of the human-object stages, values and gradients on the
