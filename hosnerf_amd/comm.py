@@ -14,39 +14,21 @@ from typing import Callable, List, Optional
 
 import torch
 
-from ._lib import HosLibraryError, stream_ptr
+from ._lib import HosLibraryError, argtypes_of, open_library, stream_ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libhoscomm.so")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "hoscomm.h")
 ID_BYTES = 128
 
-PROTOTYPES = {
-    "hos_comm_unique_id": [c_void_p],
-    "hos_comm_init": [c_void_p, c_int, c_int, c_void_p],
-    "hos_comm_destroy": [c_void_p],
-    "hos_comm_count": [c_void_p, c_void_p],
-    "hos_comm_rank": [c_void_p, c_void_p],
-    "hos_allreduce_sum_f32": [c_void_p, c_void_p, c_int64, c_void_p],
-    "hos_allreduce_avg_f32": [c_void_p, c_void_p, c_int64, c_void_p],
-    "hos_allreduce_max_u32": [c_void_p, c_void_p, c_int64, c_void_p],
-    "hos_allgather_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
-    "hos_allreduce_avg_f32_spans": [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "hos_crash_line_set": [ctypes.c_char_p, c_int64],
-    "hos_crash_line_clear": [],
-}
+PROTOTYPES = argtypes_of(HEADER)
 _lib = None
 
 
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HosLibraryError(f"{LIB_PATH} not found: run `make` (python -c 'import __graft_entry__ as g; g.build()')")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, c_int
-        _lib = lib
+        _lib = open_library(LIB_PATH, HEADER, versioned=False)      # hoscomm.h carries no revision of its own
     return _lib
 
 

@@ -462,8 +462,8 @@ extern "C" int hos_linear_dgrad(const float* dY, int lddy, const float* W, int l
 
 // rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows enter the sums; the rest is not read.
 // Narrow layers only (N <= 32: the canonical head, whose WGRAD runs on this file's exact-fp32 kernel in every arithmetic mode).
-extern "C" int hos_linear_wgrad_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
-                                     float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream) {
+extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
+                                float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream) {
     if (!dY || !X || !dW || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
     if (rows_dev && N > 32) return HOS_E_SHAPE;
     if ((lddy & 3) || (ldx & 3) || (K & 3)) return HOS_E_ALIGN;
@@ -493,9 +493,4 @@ extern "C" int hos_linear_wgrad_rows(const float* dY, int lddy, const float* X, 
     splits = hos_cdiv(a.nk, a.kt_per_split);
     if (narrow) return launch<32, 128, MODE_WGRAD>(a, splits, s);
     return launch<128, 128, MODE_WGRAD>(a, splits, s);
-}
-
-extern "C" int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
-                                float* db, int M, int N, int K, int splits, hos_stream_t stream) {
-    return hos_linear_wgrad_rows(dY, lddy, X, ldx, dW, ldw, db, M, N, K, splits, nullptr, stream);
 }

@@ -357,8 +357,8 @@ extern "C" int hos_embed_hannw(const float* x, const float* band_w, int num_freq
 }
 
 // rows_dev (optional, int32 [1] in device memory): only the first min(P, *rows_dev) rows are read and written.
-extern "C" int hos_embed_fourier_rows(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
-                                      float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream) {
+extern "C" int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
+                                 float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream) {
     if (!x || !E || P <= 0 || (state_size > 0 && !state)) return HOS_E_ARG;
     if (num_freqs < 1 || num_freqs > 16 || lde < 3 + 6 * num_freqs + state_size) return HOS_E_SHAPE;
     if (E2 && lde2 < 3 + 6 * num_freqs + state_size) return HOS_E_SHAPE;
@@ -370,11 +370,6 @@ extern "C" int hos_embed_fourier_rows(const float* x, int num_freqs, const float
     hipLaunchKernelGGL(embed_fourier_kernel, dim3(grid_for(P * lde)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x, num_freqs, state, state_size, (long)P, E, lde, E2, lde2, rows_dev);
     return hos_launch_status();
-}
-
-extern "C" int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
-                                 float* E, int lde, float* E2, int lde2, hos_stream_t stream) {
-    return hos_embed_fourier_rows(x, num_freqs, state, state_size, P, E, lde, E2, lde2, nullptr, stream);
 }
 
 // ================================================================================================
@@ -1031,18 +1026,13 @@ extern "C" int hos_slice_mask(const float* src, int lds, int col0, const float* 
 }
 
 // rows_dev (optional, int32 [1] in device memory): only the first min(P, *rows_dev) rows are read and written.
-extern "C" int hos_rgbsigma_grad_rows(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
-                                      const int32_t* rows_dev, hos_stream_t stream) {
+extern "C" int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
+                                 const int32_t* rows_dev, hos_stream_t stream) {
     if (!g_rgbsigma || !rgbsigma || !dz || P <= 0 || ldz < 4) return HOS_E_ARG;
     if ((ldz & 3) || (((uintptr_t)g_rgbsigma | (uintptr_t)rgbsigma | (uintptr_t)dz) & 15u)) return HOS_E_ALIGN;
     hipLaunchKernelGGL(rgbsigma_grad_kernel, dim3(grid_for(P * (ldz >> 2))), dim3(256), 0, static_cast<hipStream_t>(stream),
                        g_rgbsigma, rgbsigma, (long)P, dz, ldz, rows_dev);
     return hos_launch_status();
-}
-
-extern "C" int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
-                                 hos_stream_t stream) {
-    return hos_rgbsigma_grad_rows(g_rgbsigma, rgbsigma, P, dz, ldz, nullptr, stream);
 }
 
 extern "C" int hos_slice_pad(const float* src, int lds, int col0, int64_t P, int width, float* out, int ldo,

@@ -177,11 +177,6 @@ __global__ __launch_bounds__(256) void unpack_patches_bwd_kernel(const float* __
     }
 }
 
-// y = relu(y + bias) in place (behind hos_linear_fwd_splitk, which has no epilogue)
-__global__ __launch_bounds__(256) void bias_relu_kernel(float* __restrict__ y, const float* __restrict__ bias, long M, int N) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < M * N; e += (long)gridDim.x * 256) y[e] = fmaxf(y[e] + bias[e % N], 0.f);
-}
-
 inline int blocks_for(long total) { long b = (total + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 }  // namespace
@@ -258,9 +253,3 @@ extern "C" int hos_unpack_patches_bwd(const float* g_img, const int32_t* idx, in
 }
 
 extern "C" int hos_lpips_part_floats(int Np) { return Np > 0 ? Np * LP_CHUNKS : 0; }
-
-extern "C" int hos_bias_relu(float* y, const float* bias, int64_t M, int N, hos_stream_t stream) {
-    if (!y || !bias || M <= 0 || N <= 0) return HOS_E_ARG;
-    hipLaunchKernelGGL(bias_relu_kernel, dim3(blocks_for((long)M * N)), dim3(256), 0, static_cast<hipStream_t>(stream), y, bias, (long)M, N);
-    return hos_launch_status();
-}

@@ -1057,8 +1057,8 @@ extern "C" int hos_linear_bwd_fused(const float* dZ, int lddz, const float* X, i
 // measured 72 us of fixed cost per launch against ~30 us for the slab write + reduce).
 // rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows enter the sums (a multiple of 32 by
 // contract; rows behind it are not read).  The launch shape -- grid, slabs, reduce -- is that of the capacity M.
-extern "C" int hos_linear_wgrad_tr_rows(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
-                                        int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream) {
+extern "C" int hos_linear_wgrad_tr(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
+                                   int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream) {
     if (!dZ || !X || !dW || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
     if (N > 256 || K > 256) return HOS_E_SHAPE;
     if ((lddz & 3) || (ldx & 3) || (K & 3)) return HOS_E_ALIGN;
@@ -1072,11 +1072,6 @@ extern "C" int hos_linear_wgrad_tr_rows(const float* dZ, int lddz, const float* 
     }
     if (kt <= 4) return launch_mb<8, 4, false>(a, (size_t)ws_floats, s);
     return launch_mb<8, 8, false>(a, (size_t)ws_floats, s);
-}
-
-extern "C" int hos_linear_wgrad_tr(const float* dZ, int lddz, const float* X, int ldx, float* dW, int lddw, float* db,
-                                   int M, int N, int K, float* ws, int64_t ws_floats, hos_stream_t stream) {
-    return hos_linear_wgrad_tr_rows(dZ, lddz, X, ldx, dW, lddw, db, M, N, K, ws, ws_floats, nullptr, stream);
 }
 
 // Deferred slab reductions: between hos_mlp_bwd_defer(1) and hos_mlp_bwd_flush() every hos_linear_bwd_fused /

@@ -330,7 +330,7 @@ extern "C" int hos_adam_multi_lazy(int n, float* const* p, const float* const* g
     return hos_launch_status();
 }
 
-extern "C" int hos_version(void) { return 100; }
+extern "C" int hos_version(void) { return HOS_ABI_VERSION; }
 
 extern "C" int hos_device_count(void) {
     int n = 0;

@@ -717,8 +717,8 @@ extern "C" int hos_canonical_fold_unfold(const float* gW0f, const float* db0, co
 // kernel (hos_thin_linear_dgrad, mask_bits) consumes it; a waves's 32 columns that lie at or beyond N are not written.
 // rows_dev (optional, int32 [1] in device memory): only the first min(M, *rows_dev) rows are live -- read, computed and written;
 // the rest of X / Y / relu_bits is not touched.  *rows_dev is a multiple of 32 by contract (stage 3: n_live_rays * 128; M:1547-1551).
-extern "C" int hos_thin_linear_fwd_rows(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
-                                        int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream) {
+extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
+                                   int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream) {
     if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return HOS_E_ARG;
     if (N > 256 || K > 320 || (epilogue != HOS_EPI_NONE && epilogue != HOS_EPI_RELU)) return HOS_E_SHAPE;
     if ((ldx & 3) || (ldw & 3) || (K & 3) || (((uintptr_t)X | (uintptr_t)W) & 15u)) return HOS_E_ALIGN;
@@ -746,21 +746,16 @@ extern "C" int hos_thin_linear_fwd_rows(const float* X, int ldx, const float* W,
     return K <= 256 ? launch_thin<16, false>(a, s) : launch_thin<20, false>(a, s);
 }
 
-extern "C" int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
-                                   int M, int N, int K, int epilogue, void* relu_bits, hos_stream_t stream) {
-    return hos_thin_linear_fwd_rows(X, ldx, W, ldw, bias, Y, ldy, M, N, K, epilogue, relu_bits, nullptr, stream);
-}
-
 // dX[M, K] = (dY[M, :Npad] . W[:Npad, :K]) * [mask > 0], K <= 256 output columns, Npad <= 256 (Npad % 4 == 0; rows of W and
 // columns of dY beyond the layer's width are zero by contract).  mask: the layer's input activations [M, >= K] or NULL;
 // W and mask may start at ANY column of their matrices (4-byte aligned: the h part of a skip layer's concat row starts at
 // column 127; the mask's 16-byte groups around the window must be readable), dY and dX rows are 16-byte aligned.
 // mask_bits (optional): the bit mask hos_thin_linear_fwd wrote for the layer's input activations (its Y [M, K]); takes
 // precedence over `mask` and removes the re-read of the fp32 activations (a third of this kernel's HBM traffic).
-// rows_dev: as hos_thin_linear_fwd_rows (rows of dY, mask, mask_bits and dX at and behind the bound are not touched).
-extern "C" int hos_thin_linear_dgrad_rows(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
-                                          const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev,
-                                          hos_stream_t stream) {
+// rows_dev: as hos_thin_linear_fwd (rows of dY, mask, mask_bits and dX at and behind the bound are not touched).
+extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
+                                     const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev,
+                                     hos_stream_t stream) {
     if (!dY || !W || !dX || M <= 0 || K <= 0 || Npad <= 0) return HOS_E_ARG;
     if (K > 256 || Npad > 256) return HOS_E_SHAPE;
     if ((lddy & 3) || (Npad & 3) || (mask && (ldmask & 3)) || ((uintptr_t)dY & 15u) || (((uintptr_t)W | (uintptr_t)mask) & 3u)) return HOS_E_ALIGN;
@@ -780,9 +775,4 @@ extern "C" int hos_thin_linear_dgrad_rows(const float* dY, int lddy, const float
         if (a.bits) a.bits += (size_t)(f.M / 32) * TH_NT;
     }
     return Npad <= 128 ? launch_thin<8, true>(a, s) : launch_thin<16, true>(a, s);
-}
-
-extern "C" int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
-                                     const void* mask_bits, float* dX, int lddx, int M, int K, hos_stream_t stream) {
-    return hos_thin_linear_dgrad_rows(dY, lddy, W, ldw, Npad, mask, ldmask, mask_bits, dX, lddx, M, K, nullptr, stream);
 }

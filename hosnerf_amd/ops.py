@@ -115,7 +115,7 @@ def linear_fwd(A0: torch.Tensor, K0: int, W: torch.Tensor, bias: Optional[torch.
             and ldc is None and out is not None and _lib.load().hos_get_gemm_mode() == GEMM_BF16X3):
         # many rows through a thin layer: persistent kernel with the weight in registers (hos_thin.hip)
         _timed(f"thin_fwd[M={M},N={N},K={K0}]", 2.0 * M * N * K0, lambda: call(
-            "hos_thin_linear_fwd_rows", ptr(A0), A0.stride(0), ptr(W), W.stride(0), ptr(bias), ptr(out) + 4 * out_col0, out.stride(0),
+            "hos_thin_linear_fwd", ptr(A0), A0.stride(0), ptr(W), W.stride(0), ptr(bias), ptr(out) + 4 * out_col0, out.stride(0),
             M, N, K0, epilogue, ptr(relu_bits, torch.int16), ptr(rows_dev, torch.int32)))
         return out
     if relu_bits is not None:
@@ -282,7 +282,7 @@ def linear_dgrad(dY: torch.Tensor, W: torch.Tensor, Npad: int, K: int, out: torc
         for k0 in range(0, K, 256):
             kc = min(256, K - k0)
             _timed(f"thin_dgrad[M={M},N={kc},K={Npad}]", 2.0 * M * kc * Npad, lambda: call(
-                "hos_thin_linear_dgrad_rows", ptr(dY), dY.stride(0), wptr + 4 * k0, W.stride(0), Npad,
+                "hos_thin_linear_dgrad", ptr(dY), dY.stride(0), wptr + 4 * k0, W.stride(0), Npad,
                 None if mptr is None else mptr + 4 * k0, 0 if mask_src is None else mask_src.stride(0), ptr(mask_bits, torch.int16),
                 ptr(out) + 4 * k0, out.stride(0), M, kc, ptr(rows_dev, torch.int32)))
         return out
@@ -307,11 +307,11 @@ def linear_wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, db: Option
             kc = min(256, K - k0)
             ws = _bwd_workspace(dY.device, M, N, kc, False)
             _timed(f"wgrad_tr[M={N},N={kc},K={M}]", 2.0 * M * N * kc, lambda: call(
-                "hos_linear_wgrad_tr_rows", ptr(dY), dY.stride(0), ptr(X) + 4 * k0, X.stride(0), ptr(dW) + 4 * (w_col0 + k0), dW.stride(0),
+                "hos_linear_wgrad_tr", ptr(dY), dY.stride(0), ptr(X) + 4 * k0, X.stride(0), ptr(dW) + 4 * (w_col0 + k0), dW.stride(0),
                 ptr(db) if k0 == 0 else None, M, N, kc, ptr(ws), ws.numel(), ptr(rows_dev, torch.int32)))
         return
     _timed(f"gemm_wgrad[M={N},N={K},K={M}]", 2.0 * M * N * K, lambda: call(
-        "hos_linear_wgrad_rows", ptr(dY), dY.stride(0), ptr(X), X.stride(0), ptr(dW) + 4 * w_col0, dW.stride(0),
+        "hos_linear_wgrad", ptr(dY), dY.stride(0), ptr(X), X.stride(0), ptr(dW) + 4 * w_col0, dW.stride(0),
         ptr(db), M, N, K, splits, ptr(rows_dev, torch.int32)))
 
 
@@ -382,13 +382,6 @@ class deferred_bwd_reduce:
             _lib.check(_lib.load().hos_mlp_bwd_defer(0), "hos_mlp_bwd_defer")
             call("hos_mlp_bwd_flush")
         return False
-
-
-# Retired A/B switches.  The one-pass 128-wide layer backward (linear_bwd_fused) and the wide weight gradient on hos_mlpbwd.hip
-# (hos_linear_wgrad_tr) are the only paths and nothing in this package reads these names; they stay defined, always True, because
-# callers written against the previous revision assert them before relying on those paths (`assert ops.WGRAD_TR`).
-FUSED_THIN_BWD = True
-WGRAD_TR = True
 
 
 # ------------------------------------------------------------------------------------------ fused MLP chain (hos_chain.hip)
@@ -761,7 +754,7 @@ class _Deconv3dSharded(torch.autograd.Function):
                 call("hos_outer_accum", ptr(x) + 4 * c0, x.stride(0), ptr(dycol), dycol.stride(0), ptr(gW[c0:c0 + cs]), gW.stride(0), M, cs, Cout * 64)
             else:                           # gW[c0:c1] += x[:, c0:c1]^T @ dycol
                 call("hos_linear_wgrad", ptr(x) + 4 * c0, x.stride(0), ptr(dycol), dycol.stride(0), ptr(gW[c0:c0 + cs]), gW.stride(0),
-                     None, M, cs, Cout * 64, 0)
+                     None, M, cs, Cout * 64, 0, None)
         return dx, None, None, None, None, None
 
 
@@ -1237,7 +1230,7 @@ def embed_hannw(x, band_w, cond, E, PE=None, rows_dev=None):
 
 def embed_fourier(x, num_freqs, state, E, E2=None, rows_dev=None):
     P = x.shape[0]
-    call("hos_embed_fourier_rows", ptr(x), num_freqs, ptr(state), 0 if state is None else state.numel(), P,
+    call("hos_embed_fourier", ptr(x), num_freqs, ptr(state), 0 if state is None else state.numel(), P,
          ptr(E), E.stride(0), ptr(E2), 0 if E2 is None else E2.stride(0), ptr(rows_dev, torch.int32))
 
 
@@ -1777,7 +1770,7 @@ def slice_pad(src, col0, width, out, rows_dev=None):
 
 
 def rgbsigma_grad(g, y, dz, rows_dev=None):
-    call("hos_rgbsigma_grad_rows", ptr(g), ptr(y), y.shape[0], ptr(dz), dz.stride(0), ptr(rows_dev, torch.int32))
+    call("hos_rgbsigma_grad", ptr(g), ptr(y), y.shape[0], ptr(dz), dz.stride(0), ptr(rows_dev, torch.int32))
 
 
 def adam_step_dyn(p, g, m, v, hyper, beta1, beta2, eps, grad_scale=1.0, sumsq_buf=None, max_norm=0.0):

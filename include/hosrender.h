@@ -34,8 +34,12 @@ extern "C" {
 
 typedef void* hos_stream_t; /* hipStream_t */
 
+/* Revision of this ABI, 100*major + minor: raised by every change that removes an entry point or alters a signature.  The ctypes
+ * binding derives its prototypes from this header and refuses a library whose hos_version() is another revision. */
+#define HOS_ABI_VERSION 101
+
 /* Library / device probes (no compute). */
-int hos_version(void);                 /* 100*major + minor */
+int hos_version(void);                 /* HOS_ABI_VERSION of the build */
 int hos_device_count(void);            /* >=0, or HOS_E_NODEVICE */
 const char* hos_error_string(int code);
 
@@ -80,9 +84,13 @@ int hos_set_range_flag(unsigned int* flag);
 #define HOS_EPI_SIGMOID_RELU4 5 /* N==4: cols 0..2 sigmoid, col 3 relu (N:539-540)             */
 #define HOS_EPI_RESIDUAL 6   /* C = acc + bias + aux[m*aux_col + n]  (xyz + offset, mlp_offset.py:66; aux_col = ld of aux) */
 
-/* `rows_dev` (several entry points below; may be NULL): the number of LIVE rows of a fixed-capacity buffer, read from device
- * memory by the kernel -- rows (whole row tiles for the GEMMs) at or past it are skipped.  Used for the cycle-consistency set
- * of the human branch, whose size is data dependent (hos_compact_rows): shapes stay static, the work follows the count.
+/* `rows_dev` (several entry points below, always the last parameter before the stream; int32 [1] in device memory, NULL: all M /
+ * P rows): the number of LIVE rows of a fixed-capacity buffer, read by the kernel and clamped to the capacity M -- rows (whole
+ * row tiles for the GEMMs) at and behind min(M, *rows_dev) are skipped: neither read nor written, inputs, masks and outputs alike
+ * (they may be uninitialised memory); reductions take the live rows only.  Grid, slabs and reduction stay those of the capacity.
+ * *rows_dev is a multiple of 32 wherever a whole-tile kernel takes it (the thin layers, hos_linear_wgrad_tr).  Used for the
+ * cycle-consistency set of the human branch, whose size is data dependent (hos_compact_rows), and for the live rays of stage 3
+ * (hos_select_live_rays: live rays x 128 samples): shapes stay static, the work follows the count.
  *
  * C[M,N] = epi( [A0 | A1][M, K0+K1] @ W[N, K0+K1]^T + bias[N] ).
  * A1 may be NULL (K1 = 0); K0, K1 multiples of 32; W row n starts at W + n*ldw.  */
@@ -113,13 +121,10 @@ int hos_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npa
 
 /* dW[N,K] += dY[M,N]^T @ X[M,K]   and, if db != NULL, db[N] += column sums of dY.
  * M (the reduction dim = number of sample points) is arbitrary (tail rows are zero-filled).  Accumulates with fp32
- * atomics over `splits` partitions of M (splits <= 0: chosen by the library). */
+ * atomics over `splits` partitions of M (splits <= 0: chosen by the library).
+ * rows_dev: narrow layers only (N <= 32: the canonical head); HOS_E_SHAPE otherwise. */
 int hos_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
-                     float* db, int M, int N, int K, int splits, hos_stream_t stream);
-/* ... over a fixed-capacity buffer: only the first min(M, *rows_dev) rows enter the sums, the rest is not read (rows_dev: int32 [1]
- * in device memory, NULL: all M).  Narrow layers only (N <= 32: the canonical head); HOS_E_SHAPE otherwise. */
-int hos_linear_wgrad_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw,
-                          float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream);
+                     float* db, int M, int N, int K, int splits, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Fused backward of one thin layer (N, K <= 128) over M rows -- replaces a hos_linear_wgrad + hos_linear_dgrad pair on the
  * same (dY, X): dX [M,K] = (dY . W) masked by X > 0 (relu_mask != 0; dX NULL: skip), dW [N,ldw] += dY^T . X, db [N] += column
@@ -147,11 +152,7 @@ long long hos_mlp_bwd_ws_floats(int M, int N, int K, int fused);
  * scratch (>= 256*(256*256+256) floats) for the per-workgroup dW / db partials (NULL: fp32 atomics).  Replaces hos_linear_wgrad for M >> N, K.
  * Reference: autograd of the 256-wide nn.Linear layers of CanonicalMLP, canonical_mlps/mlp_rgb_sigma.py:49-58. */
 int hos_linear_wgrad_tr(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db,
-                        int M, int N, int K, float* ws, int64_t ws_floats, hos_stream_t stream);
-/* ... with a device-side row bound (see "Live rays" below): only the first min(M, *rows_dev) rows enter the sums and nothing behind
- * them is read; grid, slabs and reduction are those of the capacity M.  *rows_dev is a multiple of 32. */
-int hos_linear_wgrad_tr_rows(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db,
-                             int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream);
+                        int M, int N, int K, float* ws, int64_t ws_floats, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Thin layers over very many rows with the weight slice of every wave resident in registers (hos_thin.hip): N, K <= 256
  * (forward: K <= 320, the folded skip layer below).
@@ -165,16 +166,9 @@ int hos_linear_wgrad_tr_rows(const float* dY, int lddy, const float* X, int ldx,
  * Same results contract as hos_linear_fwd / hos_linear_dgrad in split mode.
  * Reference: CanonicalMLP, canonical_mlps/mlp_rgb_sigma.py:49-58 (256-wide Linear + ReLU chain at M = rays x 128). */
 int hos_thin_linear_fwd(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
-                        int M, int N, int K, int epilogue, void* relu_bits, hos_stream_t stream);
+                        int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream);
 int hos_thin_linear_dgrad(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
-                          const void* mask_bits, float* dX, int lddx, int M, int K, hos_stream_t stream);
-/* The same two launches over fixed-capacity buffers: rows_dev (int32 [1] in device memory, NULL: all M) bounds the live rows;
- * rows at and behind min(M, *rows_dev) -- of X / dY, mask, the bit mask and the output -- are neither read nor written (they are
- * uninitialised memory).  *rows_dev is a multiple of 32 (stage 3: live rays x 128 samples, see hos_select_live_rays). */
-int hos_thin_linear_fwd_rows(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy,
-                             int M, int N, int K, int epilogue, void* relu_bits, const int32_t* rows_dev, hos_stream_t stream);
-int hos_thin_linear_dgrad_rows(const float* dY, int lddy, const float* W, int ldw, int Npad, const float* mask, int ldmask,
-                               const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev, hos_stream_t stream);
+                          const void* mask_bits, float* dX, int lddx, int M, int K, const int32_t* rows_dev, hos_stream_t stream);
 
 /* CanonicalMLP with the state embedding folded into biases.  The reference concatenates ONE state vector per call to every
  * point's Fourier features (core/nets/human_nerf/network.py:177-230 picks it by frame time and expands it over the points), so its columns of the input
@@ -469,10 +463,7 @@ int hos_embed_hannw(const float* x, const float* band_w, int num_freqs, const fl
  * (embedders/fourier.py:11-57, N:248-249); E2 (optional) receives the same 3+6F+state_size columns
  * (the skip-concat buffer of mlp_rgb_sigma.py:52-53). */
 int hos_embed_fourier(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
-                      float* E, int lde, float* E2, int lde2, hos_stream_t stream);
-/* ... only the first min(P, *rows_dev) rows (rows_dev: int32 [1] in device memory, NULL: all P). */
-int hos_embed_fourier_rows(const float* x, int num_freqs, const float* state, int state_size, int64_t P,
-                           float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream);
+                      float* E, int lde, float* E2, int lde2, const int32_t* rows_dev, hos_stream_t stream);
 
 /* Backward of hos_human_sample_warp w.r.t. the motion-weight volume (atomics into g_vol [K,V,V,V]) and the
  * backward motion basis (g_R [K,9], g_T [K,3], accumulated with atomics -- caller zeroes them):
@@ -505,10 +496,7 @@ int hos_slice_pad(const float* src, int lds, int col0, int64_t P, int width, flo
 /* dz[p, 0..3] = g * (sigmoid' | relu') evaluated from the activated outputs (N:539-540); the whole [P, ldz] row is written
  * (columns 4.. zero; ldz % 4 == 0, 16-byte aligned pointers). */
 int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
-                      hos_stream_t stream);
-/* ... only the first min(P, *rows_dev) rows (rows_dev: int32 [1] in device memory, NULL: all P). */
-int hos_rgbsigma_grad_rows(const float* g_rgbsigma, const float* rgbsigma, int64_t P, float* dz, int ldz,
-                           const int32_t* rows_dev, hos_stream_t stream);
+                      const int32_t* rows_dev, hos_stream_t stream);
 
 /* NeRF-style composite `_raw2outputs` (M:73-99; S2 form N2:273-299 with the activations applied by
  * the MLP epilogue): dists = [dz..., last_dist]*|d|; alpha = (1-exp(-sigma*dists))*mask;
@@ -675,7 +663,7 @@ int hos_scatter_rows(const float* src, const int32_t* sel, const int32_t* count,
  *                         rows at and behind *rows_live zero.
  *   hos_scatter_rays:     the inverse (dst [B*S, C] from the front of src; rows of background rays zero).  Each is the other's
  *                         gradient.  src and dst must not overlap.
- * No host read, fixed shapes: the count stays in device memory and bounds the launches in between (the *_rows entry points). */
+ * No host read, fixed shapes: the count stays in device memory and bounds the launches in between (their `rows_dev`). */
 int hos_select_live_rays(const float* mask, float thr, int B, int S, int32_t* ray_ids, int32_t* flag, int32_t* rows_live,
                          hos_stream_t stream);
 int hos_gather_rays(const float* src, const int32_t* ray_ids, const int32_t* rows_live, int B, int S, int C, float* dst,
@@ -819,7 +807,6 @@ int hos_adam_multi_lazy(int n, float* const* p, const float* const* g, float* co
  *                         chunk; R = sqrt(sum f^2 + 1e-10) + 1e-10   (lpips.py:92-100)
  *   hos_lpips_head_bwd    g_feats [Np * HW, C] (+)= gscale[0] * coef * d/d f0, times [f0 > 0]
  *   hos_lpips_finish      out[0] = sum of part, in index order
- *   hos_bias_relu         y = relu(y + bias) in place: the epilogue behind hos_linear_fwd_splitk for the deep, few-pixel convolutions
  *   hos_unpack_patches_fwd/bwd  model.py:41-50 `_unpack_imgs`: img[p] = idx[p] >= 0 ? rgb[idx[p]] : bgcolor * bg_scale;  backward
  *                         g_rgb[idx[p]] = g_img[p] * (s0, s1, s2) per channel (the caller zeroes g_rgb) */
 int hos_lpips_prep(const float* x01, int64_t n_pixels, float* out, hos_stream_t stream);
@@ -832,7 +819,6 @@ int hos_lpips_head_bwd(const float* feats, const float* lin_w, int Np, int HW, i
                        int accumulate, float* g_feats, hos_stream_t stream);
 int hos_lpips_finish(const float* part, int Np, float* out, hos_stream_t stream);
 int hos_lpips_part_floats(int Np);
-int hos_bias_relu(float* y, const float* bias, int64_t M, int N, hos_stream_t stream);
 int hos_unpack_patches_fwd(const float* rgb, const int32_t* idx, const float* bgcolor, float bg_scale, int64_t n_pixels, float* img,
                            hos_stream_t stream);
 int hos_unpack_patches_bwd(const float* g_img, const int32_t* idx, int64_t n_pixels, float s0, float s1, float s2, float* g_rgb,

@@ -372,3 +372,100 @@ def test_lazy_spans_cover_exactly_the_parameters_that_can_be_without_a_gradient(
     assert r == [(0, 8, 1.0), (8, 8, 1.0), (16, 4, 0.1), (20, 12, 0.1)] and idx == [None, (0, 2, 4), (2, 1, 4), None]
     with pytest.raises(ValueError):
         _split_at_lazy([(0, 100, 1.0), (100, 60, 0.1)], [(98, 4)])      # a span may not straddle two learning rates
+
+
+_SNIPPET = """
+/* a comment that mentions hos_foo(int x); and spans
+ * two lines */
+#ifndef SNIPPET_H
+#define HOS_ABI_VERSION 7
+typedef void* hos_handle_t;   // hos_bar( in a line comment
+#ifdef __cplusplus
+extern "C" {
+#endif
+int hos_a(const float* x, float* const* tbl, void* p, const void* q, unsigned int* u, const int32_t* i, const int64_t* l);
+int hos_b(int a, int32_t b, float c, int64_t d, long long e, hos_handle_t h);
+int hos_c(void);
+const char* hos_d(const char* line,
+                  int64_t len,
+                  hos_handle_t* out);
+long long hos_e(int n);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_on_a_literal_snippet(tmp_path):
+    """Every spelling the two headers use, with the expected ctypes written out; an unknown type raises, it never becomes int."""
+    from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+    from hosnerf_amd import _lib
+    path = tmp_path / "snippet.h"
+    path.write_text(_SNIPPET)
+    assert _lib.parse_header(str(path)) == {
+        "hos_a": (c_int, [c_void_p] * 7),
+        "hos_b": (c_int, [c_int, c_int, c_float, c_int64, c_int64, c_void_p]),
+        "hos_c": (c_int, []),
+        "hos_d": (c_char_p, [c_char_p, c_int64, c_void_p]),
+        "hos_e": (c_int64, [c_int]),
+    }
+    assert _lib.abi_version(str(path)) == 7
+    for k, bad in enumerate(("int hos_f(double x);", "double hos_f(int x);", "int hos_f(hos_other_t h);", "int hos_f(int x) { return x; }")):
+        other = tmp_path / f"bad{k}.h"
+        other.write_text("typedef void* hos_handle_t;\n" + bad + "\n")
+        with pytest.raises(_lib.HosLibraryError, match="hos_f"):
+            _lib.parse_header(str(other))
+    with pytest.raises(_lib.HosLibraryError, match="missing.h"):
+        _lib.parse_header(str(tmp_path / "missing.h"))
+
+
+def test_header_parser_finds_every_declaration_of_the_real_headers():
+    from hosnerf_amd import _lib, comm
+    for header, lib, protos in ((_lib.HEADER, _lib.load(), _lib.PROTOTYPES), (comm.HEADER, comm.load(), comm.PROTOTYPES)):
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(header).read(), flags=re.S)
+        names = set(re.findall(r"\b(hos_[a-z0-9_]+)\s*\(", text)) - set(re.findall(r"typedef\s+void\s*\*\s*(\w+)\s*;", text))
+        parsed = _lib.parse_header(header)
+        assert os.path.dirname(header) == os.path.join(ROOT, "include") and len(names) >= 12
+        assert len(parsed) == len(names) and set(parsed) == names
+        assert protos == {n: a for n, (_, a) in parsed.items()}
+        for n, (restype, argtypes) in parsed.items():
+            assert hasattr(lib, n), f"{n} is declared in {header} and not exported"
+            assert getattr(lib, n).argtypes == argtypes and getattr(lib, n).restype is restype
+
+
+_MERGED = {"hos_thin_linear_fwd": 14, "hos_thin_linear_dgrad": 14, "hos_linear_wgrad": 13, "hos_linear_wgrad_tr": 14,
+           "hos_embed_fourier": 11, "hos_rgbsigma_grad": 7}
+
+
+def test_merged_row_bound_entry_points_take_the_new_arity():
+    """One name per kernel, `rows_dev` before the stream: all-zero arguments at the new count are rejected before any launch; the
+    old count is a ctypes error, and the twins and hos_bias_relu are gone."""
+    import ctypes
+    from hosnerf_amd import _lib
+    lib = _lib.load()
+    for name, n in _MERGED.items():
+        assert len(_lib.PROTOTYPES[name]) == n and _lib.PROTOTYPES[name][-2:] == [_lib._P, _lib._P]
+        assert getattr(lib, name)(*([0] * n)) == -1                        # HOS_E_ARG
+        with pytest.raises(TypeError):
+            getattr(lib, name)(*([0] * (n - 1)))
+        assert not hasattr(lib, name + "_rows") and name + "_rows" not in _lib.PROTOTYPES
+    assert not hasattr(lib, "hos_bias_relu") and "hos_bias_relu" not in _lib.PROTOTYPES
+    # hos_linear_wgrad keeps its own restriction: a row bound on a layer wider than 32 is a shape error, before any launch
+    buf = (ctypes.c_float * 4)()
+    a = ctypes.addressof(buf)
+    assert lib.hos_linear_wgrad(a, 64, a, 64, a, 64, 0, 64, 33, 64, 0, a, 0) == -3
+
+
+def test_library_of_another_abi_revision_is_refused(tmp_path):
+    from hosnerf_amd import _lib
+    want = _lib.abi_version(_lib.HEADER)
+    assert want >= 101 and _lib.load().hos_version() == want
+    text = open(_lib.HEADER).read()
+    assert text.count("#define HOS_ABI_VERSION %d" % want) == 1
+    other = tmp_path / "hosrender.h"
+    other.write_text(text.replace("#define HOS_ABI_VERSION %d" % want, "#define HOS_ABI_VERSION 999"))
+    with pytest.raises(_lib.HosLibraryError, match="rebuild"):
+        _lib.open_library(_lib.LIB_PATH, str(other))
+    with pytest.raises(_lib.HosLibraryError, match="nowhere.h"):
+        _lib.open_library(_lib.LIB_PATH, str(tmp_path / "nowhere.h"))

@@ -573,21 +573,21 @@ def test_thin_and_fused_entry_points_small_m(dev, M):
     Xd, Wd, bd, dYd = X.to(dev), W.to(dev), b.to(dev), dY.to(dev)
     Y = torch.full((M, N), float("nan"), device=dev)
     bits = torch.zeros(((M + 31) // 32) * 512, dtype=torch.int16, device=dev)
-    call("hos_thin_linear_fwd", ptr(Xd), K, ptr(Wd), K, ptr(bd), ptr(Y), N, M, N, K, 1, ptr(bits, torch.int16))
+    call("hos_thin_linear_fwd", ptr(Xd), K, ptr(Wd), K, ptr(bd), ptr(Y), N, M, N, K, 1, ptr(bits, torch.int16), None)
     want = torch.relu(X.double() @ W.double().t() + b.double())
     assert float((Y.double().cpu() - want).abs().max()) < 2e-6 * max(1.0, float(want.abs().max()))
     dX = torch.full((M, K), float("nan"), device=dev)
-    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, ptr(Xd), K, None, ptr(dX), K, M, K)
+    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, ptr(Xd), K, None, ptr(dX), K, M, K, None)
     want = (dY.double() @ W.double()) * (X > 0)
     assert float((dX.double().cpu() - want).abs().max()) < 2e-5 * float(want.abs().max())
     # the same product masked by the forward launch's ReLU BITS (mask of Y, N == K here) == masked by the fp32 Y: bit-equal
     dXf = torch.full((M, K), float("nan"), device=dev); dXb = torch.full((M, K), float("nan"), device=dev)
-    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, ptr(Y), N, None, ptr(dXf), K, M, K)
-    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, None, 0, ptr(bits, torch.int16), ptr(dXb), K, M, K)
+    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, ptr(Y), N, None, ptr(dXf), K, M, K, None)
+    call("hos_thin_linear_dgrad", ptr(dYd), N, ptr(Wd), K, N, None, 0, ptr(bits, torch.int16), ptr(dXb), K, M, K, None)
     assert torch.equal(dXf, dXb)
     assert float((dXf == 0).float().mean()) > 0.2          # the mask did something
     dW = torch.zeros(N, K, device=dev); db = torch.zeros(N, device=dev)
-    call("hos_linear_wgrad_tr", ptr(dYd), N, ptr(Xd), K, ptr(dW), K, ptr(db), M, N, K, None, 0)
+    call("hos_linear_wgrad_tr", ptr(dYd), N, ptr(Xd), K, ptr(dW), K, ptr(db), M, N, K, None, 0, None)
     want = dY.double().t() @ X.double()
     assert float((dW.double().cpu() - want).abs().max()) < 3e-5 * float(want.abs().max())
     assert float((db.double().cpu() - dY.double().sum(0)).abs().max()) < 3e-5 * float(dY.double().sum(0).abs().max()) + 1e-8
