@@ -2,6 +2,7 @@
 //
 //   hos_alpha_weights_{fwd,bwd}   H:235-261  compute_alpha_weights
 //   hos_volrender_{fwd,bwd}       H:265-275  volumetric_rendering
+//   hos_volrender_maps_fwd        H:265-275 + H:197-223  the same rendering with opacity, expected and median distance
 //   hos_interlevel_{fwd,bwd}      M1:611-620 -> H:136-138 / H:117-132 / H:109-114
 //   hos_distortion_{fwd,bwd}      M1:622-627 -> H:142-149
 //   hos_head_grad                 softplus' / sigmoid' of M:316, M:345-346
@@ -120,21 +121,73 @@ __global__ __launch_bounds__(256) void alpha_weights_bwd_kernel(const float* __r
     }
 }
 
+// volumetric_rendering (H:265-275).  The VolMaps instantiation is hos_volrender_maps_fwd: the same strided loop and the same wave_sum
+// order (rgb is bit-identical), plus acc = sum w (H:270, the value the background term uses), depth = sum w (t_s + t_{s+1}) / 2 and
+// the median distance sorted_interp(0.5, integrate_weights(w), tdist) (H:197-204, H:208-223).  The CDF's knot s + 1 is
+// min(sum_{j<=s} w_j, 1), knot S is 1: the sum runs in sample order, a wave inclusive scan per 64-sample pass plus the carry of the
+// passes before.  Prefixes from a tree scan need not be monotone in fp32, so the bin is DEFINED by the first knot above 0.5 (ballot,
+// lowest pass first) and k is the knot before it: cw_k <= 0.5 < cw_{k+1}, the denominator is positive and the reference's nan_to_num
+// has nothing to do.  VolNoMaps is an empty trailing argument: the rgb-only instantiation is the kernel it was before the maps.
+struct VolNoMaps { static constexpr bool on = false; };
+struct VolMaps {
+    static constexpr bool on = true;
+    const float* tdist;                // [B,S+1]
+    float *acc, *depth, *median;       // [B] each, any of them NULL
+};
+
+template <class M>
 __global__ __launch_bounds__(256) void volrender_fwd_kernel(const float* __restrict__ rgbs,
                                                             const float* __restrict__ weights, int B, int S,
-                                                            float bg, float* __restrict__ rgb) {
+                                                            float bg, float* __restrict__ rgb, M m) {
     const int lane = threadIdx.x & 63, ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= B) return;
     float acc = 0.f, r = 0.f, g = 0.f, b = 0.f;
+    [[maybe_unused]] float depth = 0.f;
     for (int s = lane; s < S; s += 64) {
         const float w = weights[(size_t)ray * S + s];
         const float* c = rgbs + ((size_t)ray * S + s) * 3;
         acc += w; r += w * c[0]; g += w * c[1]; b += w * c[2];
+        if constexpr (M::on) {
+            if (m.depth) {
+                const float* t = m.tdist + (size_t)ray * (S + 1) + s;
+                depth += w * (0.5f * (t[0] + t[1]));
+            }
+        }
     }
     acc = wave_sum(acc); r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
     if (lane == 0) {
         const float bgw = fmaxf(1.f - acc, 0.f) * bg;
         rgb[ray * 3 + 0] = r + bgw; rgb[ray * 3 + 1] = g + bgw; rgb[ray * 3 + 2] = b + bgw;
+    }
+    if constexpr (M::on) {
+        if (m.depth) {
+            depth = wave_sum(depth);
+            if (lane == 0) m.depth[ray] = depth;
+        }
+        if (m.acc && lane == 0) m.acc[ray] = acc;
+        if (!m.median) return;
+        float carry = 0.f, cw0 = 0.f, cw1 = 1.f;      // sum of the passes before; the two knots around the crossing
+        int k = -1;                                    // the crossing's bin; knot S is 1, so one is always found
+        for (int s0 = 0; s0 < S && k < 0; s0 += 64) {  // wave-uniform: all 64 lanes take part in the scan and the shuffles
+            const int s = s0 + lane;
+            const float w = s < S ? weights[(size_t)ray * S + s] : 0.f;
+            const float sum = wave_incl_scan(w, lane) + carry;
+            const float cw = s == S - 1 ? 1.f : fminf(sum, 1.f);
+            const unsigned long long hit = __ballot(s < S && cw > 0.5f);
+            if (hit) {
+                const int first = __ffsll(hit) - 1;
+                const float below = __shfl(cw, first > 0 ? first - 1 : 0, 64);
+                k = s0 + first;
+                cw1 = __shfl(cw, first, 64);
+                cw0 = first > 0 ? below : fminf(carry, 1.f);
+            }
+            carry = __shfl(sum, 63, 64);
+        }
+        if (lane == 0 && k >= 0) {
+            const float t0 = m.tdist[(size_t)ray * (S + 1) + k], t1 = m.tdist[(size_t)ray * (S + 1) + k + 1];
+            const float offset = fminf(fmaxf((0.5f - cw0) / (cw1 - cw0), 0.f), 1.f);
+            m.median[ray] = t0 + offset * (t1 - t0);
+        }
     }
 }
 
@@ -320,8 +373,16 @@ extern "C" int hos_alpha_weights_bwd(const float* g_weights, const float* densit
 extern "C" int hos_volrender_fwd(const float* rgbs, const float* weights, int B, int S, float bg, float* rgb,
                                  hos_stream_t stream) {
     if (!rgbs || !weights || !rgb || B <= 0 || S <= 0) return HOS_E_ARG;
-    hipLaunchKernelGGL(volrender_fwd_kernel, dim3(ray_blocks(B)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       rgbs, weights, B, S, bg, rgb);
+    hipLaunchKernelGGL(volrender_fwd_kernel<VolNoMaps>, dim3(ray_blocks(B)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       rgbs, weights, B, S, bg, rgb, VolNoMaps{});
+    return hos_launch_status();
+}
+
+extern "C" int hos_volrender_maps_fwd(const float* rgbs, const float* weights, const float* tdist, int B, int S, float bg,
+                                      float* rgb, float* acc, float* depth, float* depth_median, hos_stream_t stream) {
+    if (!rgbs || !weights || !tdist || !rgb || B <= 0 || S <= 0 || S > 64 * CH) return HOS_E_ARG;
+    hipLaunchKernelGGL(volrender_fwd_kernel<VolMaps>, dim3(ray_blocks(B)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       rgbs, weights, B, S, bg, rgb, VolMaps{tdist, acc, depth, depth_median});
     return hos_launch_status();
 }
 

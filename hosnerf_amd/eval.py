@@ -191,7 +191,10 @@ def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = Fal
     return (rendered, u8) if want_u8 else rendered
 
 
-def render_bkgd_frame(model, bank, frame_or_pose, chunk: int, train_frac: float, near: float, far: float) -> torch.Tensor:
+BKGD_FRAME_MAPS = {"rgb": "rgb", "alpha": "acc", "depth": "depth", "depth_median": "depth_median"}     # frame key -> rendering key
+
+
+def render_bkgd_frame(model, bank, frame_or_pose, chunk: int, train_frac: float, near: float, far: float, maps: bool = False):
     """One whole frame of the stage-1 background model, the loop of `trainer.test` / `trainer.predict` over `render_rays`
     (1st_State-Conditional_Scene/src/model/mipnerf360/model.py:516-534): for each `chunk` (= `LitData.chunk`) rays of the frame,
     `model(batch, train_frac, False, False, near, far)` and the last level's colour.  `model` is the `MipNeRF360`, `bank` a
@@ -201,7 +204,11 @@ def render_bkgd_frame(model, bank, frame_or_pose, chunk: int, train_frac: float,
     `randomized=False` reaches the resampling kernel (no jitter: bin centres, `sample_intervals`), the only place the reference's
     forward uses it with its shipped configuration (density / bottleneck noise are 0 and refused otherwise by `MipNeRF360MLP`);
     `is_train=False` only selects how the reference evaluates the contraction's Jacobian (helper.py:40-52, the same numbers), so
-    the model needs nothing further for this mode.  No autograd, and the module's training flag is left as it was."""
+    the model needs nothing further for this mode.  No autograd, and the module's training flag is left as it was.
+
+    `maps=True` returns a dict of whole-frame device buffers instead: `rgb` [H*W,3] (the same colours), `alpha` [H*W] (the last
+    level's `acc`, under stage 3's key name), `depth` [H*W] (sum w t_mid, not divided by alpha) and `depth_median` [H*W] (the
+    distance at which the weight CDF crosses 0.5), all from `model(..., maps=True)`: the same chunk loop, one `cat` per key."""
     if isinstance(frame_or_pose, tuple):
         kind, idx = frame_or_pose
         if kind not in ("frame", "pose"):
@@ -217,9 +224,11 @@ def render_bkgd_frame(model, bank, frame_or_pose, chunk: int, train_frac: float,
     with torch.no_grad():
         for start in range(0, n, chunk):
             batch = rays(int(idx), start, min(chunk, n - start))
-            rend, _ = model(batch, train_frac, False, False, near, far)
-            parts.append(rend[-1]["rgb"])
-    return torch.cat(parts, 0)
+            rend, _ = model(batch, train_frac, False, False, near, far, maps=maps)
+            parts.append(rend[-1])
+    if maps:
+        return {key: torch.cat([p[k] for p in parts], 0) for key, k in BKGD_FRAME_MAPS.items()}
+    return torch.cat([p["rgb"] for p in parts], 0)
 
 
 def psnr_each(img_pred: torch.Tensor, img_gt: torch.Tensor) -> float:

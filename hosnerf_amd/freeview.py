@@ -143,3 +143,21 @@ def save_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W:
     straight = np.where(ah[..., None] > 0.0, colour / np.where(ah > 0.0, ah, 1.0)[..., None], 0.0)
     Image.fromarray(np.concatenate([to8(straight), to8(ah)[..., None]], -1), mode="RGBA").save(paths["human.png"])
     return paths
+
+
+def save_bkgd_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W: int) -> Dict[str, str]:
+    """Write the maps of one stage-1 frame (`eval.render_bkgd_frame(maps=True)`) next to its colour image; returns {kind: path}:
+      <name>_depth.npy / <name>_depth_median.npy   float32 [H,W], un-normalised: sum w t_mid and the median distance (stage 1's helper.py:166-190)
+      <name>_depth.png / <name>_depth_median.png   their 8-bit previews (`depth_preview`)
+      <name>_alpha.png                             opacity sum w (helper.py:233), 8-bit greyscale"""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    kinds = ("depth.npy", "depth_median.npy", "depth.png", "depth_median.png", "alpha.png")
+    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in kinds}
+    host = {k: np.asarray(maps[k].detach().float().cpu() if isinstance(maps[k], torch.Tensor) else maps[k], dtype=np.float32).reshape(H, W)
+            for k in ("depth", "depth_median", "alpha")}
+    for k in ("depth", "depth_median"):
+        np.save(paths[k + ".npy"], host[k])
+        Image.fromarray(depth_preview(host[k])).save(paths[k + ".png"])
+    Image.fromarray((np.clip(host["alpha"], 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)).save(paths["alpha.png"])
+    return paths

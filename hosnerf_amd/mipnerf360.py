@@ -622,13 +622,25 @@ class MipNeRF360(FlatModule):
             self._level0_cache = cache = (key, sd, torch.ones(B, 1, device=dev))
         return cache[1], cache[2]
 
-    def forward(self, batch, train_frac, randomized, is_train, near, far, jitters=None, want_index: bool = False):
+    def forward(self, batch, train_frac, randomized, is_train, near, far, jitters=None, want_index: bool = False,
+                maps: bool = False):
         """`self.gemm_mode` (None = the process default, ops.set_gemm_mode) selects the arithmetic of THIS module's GEMMs;
-        without autograd the fp16 range guard may set it to exact fp32 (ops.guarded_forward)."""
-        return ops.guarded_forward(self, batch["rays_o"].device,
-                                   lambda: self._forward(batch, train_frac, randomized, is_train, near, far, jitters, want_index))
+        without autograd the fp16 range guard may set it to exact fp32 (ops.guarded_forward).
 
-    def _forward(self, batch, train_frac, randomized, is_train, near, far, jitters=None, want_index: bool = False):
+        `maps=True` (evaluation only: `is_train=False` under `torch.no_grad()`, stage 1 only) renders the last level with
+        `ops.volrender_maps` instead of `ops.volumetric_rendering`: `renderings[-1]` keeps the same `rgb` and gains `acc`, `depth`
+        (sum w t_mid, not divided by acc) and `depth_median` [B] from that one launch.  They carry no gradient."""
+        if maps and (is_train or torch.is_grad_enabled()):
+            raise ValueError("MipNeRF360.forward(maps=True) is an evaluation output: call it with is_train=False under torch.no_grad() "
+                             "(opacity / depth carry no gradient; the reference has no loss on them)")
+        if maps and not self.render_levels:
+            raise ValueError("MipNeRF360.forward(maps=True) renders the levels (stage 1); a render_levels=False model is stage 3's "
+                             "background branch, whose maps are HOSNeRF.render_bkg_only(maps=True)")
+        return ops.guarded_forward(self, batch["rays_o"].device,
+                                   lambda: self._forward(batch, train_frac, randomized, is_train, near, far, jitters, want_index, maps))
+
+    def _forward(self, batch, train_frac, randomized, is_train, near, far, jitters=None, want_index: bool = False,
+                 maps: bool = False):
         rays_o = batch["rays_o"].contiguous()
         rays_d = batch["rays_d"].contiguous()
         viewdirs = batch["viewdirs"].contiguous()
@@ -670,6 +682,8 @@ class MipNeRF360(FlatModule):
             if want_index:
                 res["bin_idx"] = out[2]
             ray_history.append(res)
-            if self.render_levels:
+            if self.render_levels and maps and not is_prop:
+                renderings.append(ops.volrender_maps(res["rgb"], weights, tdist, self.bg_intensity_range[0]))
+            elif self.render_levels:
                 renderings.append({"rgb": ops.volumetric_rendering(res["rgb"], weights, self.bg_intensity_range[0])})
         return renderings, ray_history

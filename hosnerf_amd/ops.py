@@ -1026,6 +1026,31 @@ def volumetric_rendering(rgbs, weights, bg_rgb: float):
     return _VolRender.apply(rgbs.contiguous(), weights.contiguous(), bg_rgb)
 
 
+BKGD_MAP_KEYS = ("acc", "depth", "depth_median")
+
+
+def volrender_maps(rgbs, weights, tdist, bg_rgb: float, want=BKGD_MAP_KEYS):
+    """The forward of `volumetric_rendering` with the maps of a stage-1 ray, ONE launch (hos_volrender_maps_fwd): a dict with `rgb`
+    [B,3] (bit-identical to `volumetric_rendering`) and, for every name in `want`, `acc` [B] = sum w (H:270), `depth` [B] = sum w
+    (t_s + t_{s+1}) / 2 (units of the ray parameter t, not divided by acc) and `depth_median` [B] = sorted_interp(0.5,
+    integrate_weights(w), tdist) (H:197-223), the distance at which the ray's weight CDF crosses 0.5.
+    Forward only: inputs are detached and nothing returned here is part of an autograd graph."""
+    unknown = [k for k in want if k not in BKGD_MAP_KEYS]
+    if unknown:
+        raise ValueError(f"volrender_maps: unknown map(s) {unknown}; choose from {BKGD_MAP_KEYS}")
+    rgbs, weights, tdist = (t.detach().contiguous() for t in (rgbs, weights, tdist))
+    B, S = weights.shape
+    if tuple(tdist.shape) != (B, S + 1) or tuple(rgbs.shape) != (B, S, 3):
+        raise ValueError(f"volrender_maps: rgbs {tuple(rgbs.shape)}, weights {tuple(weights.shape)}, tdist {tuple(tdist.shape)} "
+                         "are not [B,S,3], [B,S], [B,S+1]")
+    out = {"rgb": torch.empty(B, 3, device=weights.device)}
+    for k in want:
+        out[k] = torch.empty(B, device=weights.device)
+    call("hos_volrender_maps_fwd", ptr(rgbs), ptr(weights), ptr(tdist), B, S, float(bg_rgb), ptr(out["rgb"]),
+         *[ptr(out.get(k)) for k in BKGD_MAP_KEYS])
+    return out
+
+
 class _Interlevel(torch.autograd.Function):
     """sum over rays and NeRF bins of lossfun_outer(c, w, cp, wp) (H:136-138); grad w.r.t. wp only."""
 

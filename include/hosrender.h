@@ -408,6 +408,18 @@ int hos_volrender_fwd(const float* rgbs, const float* weights, int B, int S, flo
                       hos_stream_t stream);
 int hos_volrender_bwd(const float* g_rgb, const float* rgbs, const float* weights, int B, int S,
                       float bg, float* g_rgbs, float* g_weights, hos_stream_t stream);
+/* hos_volrender_fwd with the maps of a stage-1 ray from the same launch (forward only; S <= 256, HOS_E_ARG otherwise); tdist [B,S+1].
+ * rgb [B,3] is bit-identical to hos_volrender_fwd.  Each of the three map pointers may be NULL:
+ *   acc [B]          = sum_s w_s (H:270; stage 1's helper.py:233), the value the background term of rgb uses;
+ *   depth [B]        = sum_s w_s (t_s + t_{s+1}) / 2, in units of the ray parameter t, NOT divided by acc;
+ *   depth_median [B] = sorted_interp(0.5, integrate_weights(w), tdist) (H:197-204, H:208-223; stage 1's helper.py:166-190): knot 0 of the CDF is 0, knot i
+ *                      (1 <= i <= S-1) is min(sum_{s<i} w_s, 1), knot S is 1; the weights are taken as they are (not renormalised),
+ *                      so with acc < 0.5 and no opaque background the crossing falls in the last interval, as in the reference.
+ * The cumulative sum runs in sample order (a wave inclusive scan per 64 samples plus a carry).  Such prefixes need not be monotone in
+ * fp32, so the bin is defined by the FIRST knot whose CDF exceeds 0.5 and k is the knot before it: cw_k <= 0.5 < cw_{k+1}, the
+ * denominator is positive (no NaN handling), offset = clip((0.5 - cw_k) / (cw_{k+1} - cw_k), 0, 1), result t_k + offset (t_{k+1} - t_k). */
+int hos_volrender_maps_fwd(const float* rgbs, const float* weights, const float* tdist, int B, int S, float bg,
+                           float* rgb, float* acc, float* depth, float* depth_median, hos_stream_t stream);
 
 /* Stage-1 losses (M1:611-627 -> H:136-149).  Per-ray partial losses are written to loss_ray [B]
  * (the host sums / means them); the backward kernels take the upstream scale g (dLoss/dmean / B).

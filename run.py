@@ -335,16 +335,20 @@ def load_ray_bank(scene_dir: str, dev, near: float, far: float):
     return RayBank(scene, px["images"], px["alphas"], device=dev, split=split)
 
 
-def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool, chunk: int):
+def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool, chunk: int,
+                             render_maps: bool = False):
     """`trainer.test` / `trainer.predict` of the stage-1 launcher (S1/run.py, S1/src/model/mipnerf360/model.py:516-534, :582-609,
     S1/src/model/interface.py:137-150) from `last.ckpt`: the whole frames of the test split `i_test` through `eval.render_bkgd_frame`
     -> <logdir>/render_model/image{NNN}.jpg + <logdir>/results.json (PSNR as `psnr_each`; SSIM / LPIPS are not computed), and the
     cameras of the interpolated path `render_poses` / `render_times` -> <logdir>/render_video/image{NNN}.jpg (`--render_limit` stops
     early; no mp4).  `train_frac` is the checkpoint's global_step / run.max_steps.  With several ranks the FRAMES are dealt
     round-robin (as `render_tpose`), each rank writes its own files, and one all-reduce of the per-frame PSNR vector precedes rank
-    0's results.json."""
+    0's results.json.  `render_maps` (`run.render_maps`): every frame is rendered with `maps=True` and `freeview.save_bkgd_maps`
+    writes image{NNN}_depth / _depth_median (.npy + preview) and image{NNN}_alpha.png next to its jpg; PSNR and results.json are
+    those of the colours, which are the same."""
     from PIL import Image
     from hosnerf_amd import eval as ev, select_option
+    from hosnerf_amd.freeview import save_bkgd_maps
     from hosnerf_amd.raybank import deal_frames
     if bank is None:
         raise SystemExit("run.run_eval / run.run_render need --scene_dir (frames and cameras to render)")
@@ -357,8 +361,14 @@ def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, ru
     train_frac = step / max(int(lit.max_steps), 1)
     H, W = bank.H, bank.W
 
-    def write(folder, k, rendered):
+    def render(frame_or_pose):
+        out = ev.render_bkgd_frame(lit.model, bank, frame_or_pose, chunk, train_frac, lit.near, lit.far, maps=render_maps)
+        return (out["rgb"], out) if render_maps else (out, None)
+
+    def write(folder, k, rendered, frame_maps):
         os.makedirs(os.path.join(logdir, folder), exist_ok=True)
+        if frame_maps is not None:
+            save_bkgd_maps(os.path.join(logdir, folder), f"image{str(k).zfill(3)}", frame_maps, H, W)
         Image.fromarray(ev.to_8b_image(rendered.view(H, W, 3)).cpu().numpy()).save(os.path.join(logdir, folder, f"image{str(k).zfill(3)}.jpg"))
 
     out = {}
@@ -366,9 +376,9 @@ def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, ru
         frames = [int(i) for i in bank.i_test]
         psnrs = torch.zeros(len(frames), dtype=torch.float64)
         for j in deal_frames(len(frames), rank, world):
-            rendered = ev.render_bkgd_frame(lit.model, bank, frames[j], chunk, train_frac, lit.near, lit.far)
+            rendered, frame_maps = render(frames[j])
             psnrs[j] = ev.psnr_each(rendered, bank.truth(frames[j]))
-            write("render_model", j, rendered)
+            write("render_model", j, rendered, frame_maps)
         if world > 1:
             import torch.distributed as dist
             if dist.get_backend() == "nccl":
@@ -382,7 +392,7 @@ def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, ru
         total = len(bank.render_poses)
         count = min(total, args.render_limit) if args.render_limit > 0 else total
         for k in deal_frames(count, rank, world):
-            write("render_video", k, ev.render_bkgd_frame(lit.model, bank, ("pose", k), chunk, train_frac, lit.near, lit.far))
+            write("render_video", k, *render(("pose", k)))
         if rank == 0:
             print(f"[run] Render path: {count} of {total} cameras written to {os.path.join(logdir, 'render_video')}")
     return {"results": out}
@@ -403,7 +413,7 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     if model_name == "state_mipnerf360":
         if run_tpose:
             raise SystemExit("run.run_tpose renders the human-object network (stage 3); stage 1 has run.run_eval / run.run_render")
-        return evaluate_and_render_bkgd(args, lit, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, bkgd_chunk)
+        return evaluate_and_render_bkgd(args, lit, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, bkgd_chunk, render_maps)
     if model_name != "hosnerf":
         raise SystemExit("run.run_eval / run.run_render / run.run_tpose: full-frame rendering is the stage-1 (`state_mipnerf360`) and stage-3 (`hosnerf`) launchers'; stage 2 reports its training loss only")
     if scene is None:
