@@ -6,6 +6,9 @@
 //                                 masked alpha composite of the merged 160 samples (C3)
 //   hos_merge_composite_maps_fwd  the same forward launch + acc_map / depth_map (M:93-94) and the human / background layer sums
 //                                 (a second instantiation of the same kernel; the rgb-only one is compiled without any of it)
+//   hos_merge_composite_median_fwd / hos_raw2outputs_median_fwd
+//                                 the same launches + the median depth of the composited ray (`chain_median`): a third instantiation
+//                                 of the merge kernel and a second one of the raw2outputs kernel, the others compiled without it
 //
 // The reference does this with torch.sort + three advanced-indexing gathers + cumprod on [B,160,*]
 // temporaries.  Here a ray's 160 keys live in LDS, the (stable) sort is a rank-by-counting pass
@@ -79,7 +82,57 @@ __device__ __forceinline__ void composite_chain_bwd(const Chain& c, const float 
     for (int k = 0; k < CHM; ++k) galpha[k] = gw[k] * c.T[k] - (base + loc[k]) / (1.f - c.alpha[k] + 1e-10f);
 }
 
+// Median depth of a composited ray: sorted_interp(0.5, integrate_weights(w), [z_0 .. z_{S-1}, z_{S-1}]) (stage 1's helper.py:166-190
+// on the weights of M:73-92; the unbounded last interval has zero width).  Knot 0 of the CDF is 0, knot j + 1 belongs to sample j and
+// is min(lane base + local inclusive prefix of w, 1) -- 1 for sample S - 1 -- with the lane base the exclusive wave scan of the lane
+// totals.  Prefixes from a tree scan need not be monotone across lanes in fp32, so the bin is DEFINED by the first sample whose knot
+// exceeds 0.5 (lowest lane of the ballot, lowest k inside it: inside a lane the knots are monotone), and the knot below it is the one
+// owned by the sample before, the very value that was compared: cw0 <= 0.5 < cw1.  The denominator is therefore positive and the
+// fraction lies in [0, 1] in exact arithmetic; the clamp (and the min with z_{j+1} after the last addition) keeps the result inside
+// [z_j, z_{j+1}] whatever the rounding of the two subtractions, the division and that addition.  Sample S - 1 always hits (its knot is 1) and interpolates over zero width: a ray that never
+// reaches 0.5 gets z_{S-1} exactly.  Registers and shuffles only; every lane returns the ray's value.
+__device__ __forceinline__ float chain_median(const Chain& c, const float* zs, int S, int per, int lane) {
+    float K[CHM], run = 0.f;
+#pragma unroll
+    for (int k = 0; k < CHM; ++k) { run += c.w[k]; K[k] = run; }                         // padding samples have w = 0
+    const float incl = wave_incl_scan(run, lane);
+    float base = __shfl_up(incl, 1, 64);
+    if (lane == 0) base = 0.f;
+    int first = CHM;
+    float last = 0.f;
+#pragma unroll
+    for (int k = 0; k < CHM; ++k) {
+        const int j = lane * per + k;
+        K[k] = (j == S - 1) ? 1.f : fminf(base + K[k], 1.f);
+        if (k == per - 1) last = K[k];
+        if (first == CHM && k < per && j < S && K[k] > 0.5f) first = k;
+    }
+    const float below = __shfl_up(last, 1, 64);                                           // the knot of the last sample of lane - 1
+    const unsigned long long hit = __ballot(first < CHM);
+    const int owner = __ffsll(hit) - 1;
+    float med = 0.f;
+    if (lane == owner) {
+        float cw1 = K[0], cw0 = lane > 0 ? below : 0.f;
+#pragma unroll
+        for (int k = 1; k < CHM; ++k) if (k == first) { cw1 = K[k]; cw0 = K[k - 1]; }
+        const int j = lane * per + first;
+        const float t0 = zs[j], t1 = zs[j + 1 < S ? j + 1 : S - 1];
+        const float offset = fminf(fmaxf((0.5f - cw0) / (cw1 - cw0), 0.f), 1.f);
+        med = fminf(t0 + offset * (t1 - t0), t1);                                        // offset 1: t0 + (t1 - t0) may round past t1
+    }
+    return __shfl(med, owner, 64);
+}
+
 // ---------------------------------------------------------------------------------------- raw2outputs
+// R2ONoMedian is an empty trailing argument: that instantiation (hos_raw2outputs_fwd / _bwd, every training step) is the kernel it was
+// before the median; R2OMedian (hos_raw2outputs_median_fwd, forward only) adds chain_median over the ray's own z_vals.
+struct R2ONoMedian { static constexpr bool on = false; };
+struct R2OMedian {
+    static constexpr bool on = true;
+    float* median;                     // [B], may be NULL
+};
+
+template <class M>
 __global__ __launch_bounds__(256) void raw2outputs_kernel(
     const float* __restrict__ rgbs, int rgb_ld, const float* __restrict__ sigma, int sig_ld,
     const float* __restrict__ z, const float* __restrict__ dirs, const float* __restrict__ mask,
@@ -87,7 +140,7 @@ __global__ __launch_bounds__(256) void raw2outputs_kernel(
     float* __restrict__ rgb, float* __restrict__ acc, float* __restrict__ weights, float* __restrict__ depth,
     // backward (all NULL in forward)
     const float* __restrict__ g_rgb, const float* __restrict__ g_w, float* __restrict__ g_rgbs, int grgb_ld,
-    float* __restrict__ g_sigma, int gsig_ld, float* __restrict__ g_mask) {
+    float* __restrict__ g_sigma, int gsig_ld, float* __restrict__ g_mask, M med) {
     const int lane = threadIdx.x & 63, ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= B) return;
     const int per = (S + 63) / 64;
@@ -121,6 +174,12 @@ __global__ __launch_bounds__(256) void raw2outputs_kernel(
             rgb[ray * 3] = r; rgb[ray * 3 + 1] = g; rgb[ray * 3 + 2] = b;
             if (acc) acc[ray] = a;
             if (depth) depth[ray] = dep;
+        }
+        if constexpr (M::on) {
+            if (med.median) {                                                             // wave-uniform: all 64 lanes take part
+                const float t = chain_median(c, z + (size_t)ray * S, S, per, lane);
+                if (lane == 0) med.median[ray] = t;
+            }
         }
     } else {
         const float g0 = g_rgb[ray * 3], g1 = g_rgb[ray * 3 + 1], g2 = g_rgb[ray * 3 + 2];
@@ -171,11 +230,14 @@ struct MapsOut {
 };
 
 struct MergeMapsArgs : MergeArgs { MapsOut maps; };
+struct MergeMedianArgs : MergeMapsArgs { float* median; };                      // [B], may be NULL: chain_median of the composited samples
 
-// Args = MergeArgs: the rgb-only forward and the backward (no trace of the maps in its code); Args = MergeMapsArgs: forward + maps
+// Args = MergeArgs: the rgb-only forward and the backward (no trace of the maps in its code); Args = MergeMapsArgs: forward + maps;
+// Args = MergeMedianArgs: forward + maps + median depth (the other two are compiled without it)
 template <class Args>
 __global__ __launch_bounds__(256) void merge_composite_kernel(const Args a) {
-    constexpr bool MAPS = std::is_same<Args, MergeMapsArgs>::value;
+    constexpr bool MAPS = std::is_base_of<MergeMapsArgs, Args>::value;
+    constexpr bool MEDIAN = std::is_same<Args, MergeMedianArgs>::value;
     __shared__ MergeLds lds[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ray_raw = blockIdx.x * 4 + wave;
@@ -284,6 +346,12 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const Args a) {
                 if (mo->acc_bkg) mo->acc_bkg[ray] = bs[3];
             }
         }
+        if constexpr (MEDIAN) {
+            if (a.median) {                                                               // wave-uniform: all 64 lanes take part
+                const float t = chain_median(c, L.zs, S, per, lane);
+                if (live && lane == 0) a.median[ray] = t;
+            }
+        }
         if (live && a.total_order)
             for (int j = lane; j < St; j += 64) a.total_order[(size_t)ray * St + j] = (fg && j < S) ? L.order[j] : -1;
         if (a.hw_sorted) {
@@ -349,9 +417,23 @@ extern "C" int hos_raw2outputs_fwd(const float* rgbs, int rgb_ld, const float* s
                                    hos_stream_t stream) {
     if (!rgbs || !sigma || !z_vals || !rays_d || !rgb || B <= 0 || S <= 0) return HOS_E_ARG;
     if (S > MAXS) return HOS_E_SHAPE;
-    hipLaunchKernelGGL(raw2outputs_kernel, dim3(hos_cdiv(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(raw2outputs_kernel<R2ONoMedian>, dim3(hos_cdiv(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        rgbs, rgb_ld, sigma, sigma_ld, z_vals, rays_d, mask, bgcolor, last_dist, B, S, rgb, acc, weights,
-                       depth, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0, (float*)nullptr, 0, (float*)nullptr);
+                       depth, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0, (float*)nullptr, 0, (float*)nullptr,
+                       R2ONoMedian{});
+    return hos_launch_status();
+}
+
+extern "C" int hos_raw2outputs_median_fwd(const float* rgbs, int rgb_ld, const float* sigma, int sigma_ld, const float* z_vals,
+                                          const float* rays_d, const float* mask, const float* bgcolor, float last_dist,
+                                          int B, int S, float* rgb, float* acc, float* weights, float* depth,
+                                          float* depth_median, hos_stream_t stream) {
+    if (!rgbs || !sigma || !z_vals || !rays_d || !rgb || B <= 0 || S <= 0) return HOS_E_ARG;
+    if (S > MAXS) return HOS_E_SHAPE;
+    hipLaunchKernelGGL(raw2outputs_kernel<R2OMedian>, dim3(hos_cdiv(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       rgbs, rgb_ld, sigma, sigma_ld, z_vals, rays_d, mask, bgcolor, last_dist, B, S, rgb, acc, weights,
+                       depth, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, 0, (float*)nullptr, 0, (float*)nullptr,
+                       R2OMedian{depth_median});
     return hos_launch_status();
 }
 
@@ -362,18 +444,24 @@ extern "C" int hos_raw2outputs_bwd(const float* g_rgb, const float* g_weights, c
                                    hos_stream_t stream) {
     if (!g_rgb || !rgbs || !sigma || !z_vals || !rays_d || B <= 0 || S <= 0) return HOS_E_ARG;
     if (S > MAXS) return HOS_E_SHAPE;
-    hipLaunchKernelGGL(raw2outputs_kernel, dim3(hos_cdiv(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(raw2outputs_kernel<R2ONoMedian>, dim3(hos_cdiv(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        rgbs, rgb_ld, sigma, sigma_ld, z_vals, rays_d, mask, bgcolor, last_dist, B, S, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, g_rgb, g_weights, g_rgbs, g_rgb_ld, g_sigma,
-                       g_sigma_ld, g_mask);
+                       g_sigma_ld, g_mask, R2ONoMedian{});
     return hos_launch_status();
 }
 
-static int merge_launch(MergeArgs& a, hipStream_t s, const MapsOut* mo = nullptr) {
+static int merge_launch(MergeArgs& a, hipStream_t s, const MapsOut* mo = nullptr, float* const* median = nullptr) {
     if (!a.bkg_tdist || !a.bkg_rgb || !a.bkg_density || !a.human || !a.pts || !a.mask || !a.rays_o || !a.rays_d || !a.A)
         return HOS_E_ARG;
     if (a.B <= 0 || a.Sb <= 0 || a.Sh <= 0 || a.Sb + a.Sh > MAXS) return HOS_E_SHAPE;
-    if (mo) {
+    if (mo && median) {
+        MergeMedianArgs am{};
+        static_cast<MergeArgs&>(am) = a;
+        am.maps = *mo;
+        am.median = *median;
+        hipLaunchKernelGGL(merge_composite_kernel<MergeMedianArgs>, dim3(hos_cdiv(a.B, 4)), dim3(256), 0, s, am);
+    } else if (mo) {
         MergeMapsArgs am{};
         static_cast<MergeArgs&>(am) = a;
         am.maps = *mo;
@@ -414,6 +502,23 @@ extern "C" int hos_merge_composite_maps_fwd(const float* bkg_tdist, const float*
     if (!rgb) return HOS_E_ARG;
     const MapsOut mo{acc, depth, rgb_human, acc_human, rgb_bkg, acc_bkg};
     return merge_launch(a, static_cast<hipStream_t>(stream), &mo);
+}
+
+extern "C" int hos_merge_composite_median_fwd(const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
+                                              const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,
+                                              const float* rays_o_bkg, const float* rays_d_bkg, const float* smpl_to_world,
+                                              const int32_t* tiny_d_flag, int B, int Sb, int Sh, float thre_fg,
+                                              float* rgb, int32_t* idx_fg, int32_t* total_order,
+                                              float* acc, float* depth, float* rgb_human, float* acc_human,
+                                              float* rgb_bkg, float* acc_bkg, float* depth_median, hos_stream_t stream) {
+    MergeArgs a{};
+    a.bkg_tdist = bkg_tdist; a.bkg_rgb = bkg_rgb; a.bkg_density = bkg_density; a.human = human_rgbsigma;
+    a.pts = newsmpl_pts; a.mask = pts_mask; a.rays_o = rays_o_bkg; a.rays_d = rays_d_bkg; a.A = smpl_to_world;
+    a.tiny_d_flag = tiny_d_flag; a.B = B; a.Sb = Sb; a.Sh = Sh; a.thre_fg = thre_fg;
+    a.rgb = rgb; a.idx_fg = idx_fg; a.total_order = total_order;
+    if (!rgb) return HOS_E_ARG;
+    const MapsOut mo{acc, depth, rgb_human, acc_human, rgb_bkg, acc_bkg};
+    return merge_launch(a, static_cast<hipStream_t>(stream), &mo, &depth_median);
 }
 
 extern "C" int hos_merge_composite_bwd(const float* g_rgb, const float* g_human_weights_sorted,

@@ -80,6 +80,9 @@ def _local(tensors: Dict[str, torch.Tensor], n: int, group) -> Dict[str, torch.T
 FG_MAP_COLS = {"rgb": slice(0, 3), "alpha": 3, "depth": 4, "rgb_human": slice(5, 8), "alpha_human": 8}      # [n_fg, 9]
 BG_MAP_COLS = {"rgb": slice(0, 3), "alpha": 3, "depth": 4}                                                  # [n_bg, 5]
 FG_MAP_WIDTH, BG_MAP_WIDTH = 9, 5
+# with `median=True` one more column at the end of each list (`depth_median`); the layouts above are the ones without it
+FG_MEDIAN_COLS = dict(FG_MAP_COLS, depth_median=FG_MAP_WIDTH)                                               # [n_fg, 10]
+BG_MEDIAN_COLS = dict(BG_MAP_COLS, depth_median=BG_MAP_WIDTH)                                               # [n_bg, 6]
 
 
 def pack_maps(out: Dict[str, torch.Tensor], cols: Dict) -> torch.Tensor:
@@ -88,31 +91,40 @@ def pack_maps(out: Dict[str, torch.Tensor], cols: Dict) -> torch.Tensor:
 
 
 def assemble_maps(H: int, W: int, bgcolor, ray_mask: torch.Tensor, ray_mask_bkg: torch.Tensor, fg_packed: torch.Tensor,
-                  bg_packed: torch.Tensor) -> Dict[str, torch.Tensor]:
+                  bg_packed: torch.Tensor, median: bool = False) -> Dict[str, torch.Tensor]:
     """Scatter the two ray lists' packed maps into whole-frame buffers the way `rendered` is assembled (M:1456-1459):
     `rgb` [H*W,3] starts from bgcolor / 255 (M:1311-1313), `alpha` / `depth` [H*W] and the human layer `rgb_human` [H*W,3] /
     `alpha_human` [H*W] from zero; rays through the human box (`ray_mask`) take all five from `fg_packed` [n_fg,9], rays that
-    miss it (`ray_mask_bkg`) take rgb / alpha / depth from `bg_packed` [n_bg,5] and have no human layer."""
+    miss it (`ray_mask_bkg`) take rgb / alpha / depth from `bg_packed` [n_bg,5] and have no human layer.  `median`: both lists
+    carry one more column (`FG_MEDIAN_COLS` / `BG_MEDIAN_COLS`) and the frame gets `depth_median` [H*W], from zero like `depth`."""
     dev = fg_packed.device
     bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev).reshape(3) / 255.0
     maps = {"rgb": bg.expand(H * W, 3).clone(), "alpha": torch.zeros(H * W, device=dev), "depth": torch.zeros(H * W, device=dev),
             "rgb_human": torch.zeros(H * W, 3, device=dev), "alpha_human": torch.zeros(H * W, device=dev)}
-    for k, c in FG_MAP_COLS.items():
+    if median:
+        maps["depth_median"] = torch.zeros(H * W, device=dev)
+    for k, c in (FG_MEDIAN_COLS if median else FG_MAP_COLS).items():
         maps[k][ray_mask] = fg_packed[:, c]
-    for k, c in BG_MAP_COLS.items():
+    for k, c in (BG_MEDIAN_COLS if median else BG_MAP_COLS).items():
         maps[k][ray_mask_bkg] = bg_packed[:, c]
     return maps
 
 
 def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = False, group=None,
-                 cache_prologue: bool = True, maps: bool = False):
+                 cache_prologue: bool = True, maps: bool = False, median: bool = False):
     """One frame of `free_view` / `test_metrics` / `progress` (M:1320-1458).  `frame` carries the keys of the reference's
     evaluation batch (freeview.py:284-335).  Returns `rendered` [H*W, 3] on the device (every rank holds the whole frame
     when `group` is given).  `randomized` is False in free_view/test_metrics and True in progress (M:720-723).
 
     `maps=True` returns a dict of whole-frame device buffers instead: `rgb` [H*W,3] (the same `rendered`), `alpha` [H*W],
     `depth` [H*W] (`alpha_onlyfg, depth_onlyfg` / `bkg_alpha, bkg_depth` of the reference's frame loops, M:809-835) and the
-    human-object layer `rgb_human` [H*W,3] (premultiplied) / `alpha_human` [H*W]; see `assemble_maps`."""
+    human-object layer `rgb_human` [H*W,3] (premultiplied) / `alpha_human` [H*W]; see `assemble_maps`.  `median=True` (with
+    `maps=True` only) adds `depth_median` [H*W], the median depth of each ray's composite (`HOSNeRF.render(median=True)`), 0 on
+    pixels of neither ray list: one more column of the packed lists, so still one gather per list."""
+    if median and not maps:
+        raise ValueError("render_frame(median=True) is one of the maps: pass maps=True as well")
+    fg_cols, bg_cols = (FG_MEDIAN_COLS, BG_MEDIAN_COLS) if median else (FG_MAP_COLS, BG_MAP_COLS)
+    fg_width, bg_width = FG_MAP_WIDTH + int(median), BG_MAP_WIDTH + int(median)
     H, W = int(frame["img_height"]), int(frame["img_width"])
     dev = frame["rays_o_bkg"].device
     per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
@@ -128,10 +140,11 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
             b = dict(per_frame)
             b.update({k: (v[:, sl] if k == "rays" else v[sl]).contiguous() for k, v in fg.items()})
             if maps:
-                parts.append(pack_maps(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False, maps=True), FG_MAP_COLS))
+                parts.append(pack_maps(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False, maps=True,
+                                                  median=median), fg_cols))
             else:
                 parts.append(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False)["rgb"])
-        rgb = torch.cat(parts, 0) if parts else torch.zeros(0, FG_MAP_WIDTH if maps else 3, device=dev)
+        rgb = torch.cat(parts, 0) if parts else torch.zeros(0, fg_width if maps else 3, device=dev)
         # ---- rays that miss it: background only (M:1434-1452)
         n_bg = frame["rays_o_bkg_only"].shape[0]
         bg_rays = _local({"rays_o": frame["rays_o_bkg_only"], "rays_d": frame["rays_d_bkg_only"],
@@ -141,15 +154,15 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
             bb = {k: v[i:i + chunk_bkg].contiguous() for k, v in bg_rays.items()}
             bb["times"] = frame["time"]
             if maps:
-                parts.append(pack_maps(hos.render_bkg_only(bb, randomized=randomized, is_train=False, maps=True), BG_MAP_COLS))
+                parts.append(pack_maps(hos.render_bkg_only(bb, randomized=randomized, is_train=False, maps=True, median=median), bg_cols))
             else:
                 parts.append(hos.render_bkg_only(bb, randomized=randomized, is_train=False))
-        bkg_rgbs = torch.cat(parts, 0) if parts else torch.zeros(0, BG_MAP_WIDTH if maps else 3, device=dev)
+        bkg_rgbs = torch.cat(parts, 0) if parts else torch.zeros(0, bg_width if maps else 3, device=dev)
         if group is not None:
             rgb = gather_frame(rgb, n_fg, group) if n_fg else rgb
             bkg_rgbs = gather_frame(bkg_rgbs, n_bg, group) if n_bg else bkg_rgbs
     if maps:
-        return assemble_maps(H, W, frame.get("bgcolor", (0.0, 0.0, 0.0)), frame["ray_mask"], frame["ray_mask_bkg"], rgb, bkg_rgbs)
+        return assemble_maps(H, W, frame.get("bgcolor", (0.0, 0.0, 0.0)), frame["ray_mask"], frame["ray_mask_bkg"], rgb, bkg_rgbs, median=median)
     bg = torch.as_tensor(frame.get("bgcolor", (0.0, 0.0, 0.0)), dtype=torch.float32, device=dev).reshape(3) / 255.0
     rendered = bg.expand(H * W, 3).clone()                                        # M:1311-1313
     rendered[frame["ray_mask"]] = rgb                                             # M:1456-1459
@@ -157,7 +170,7 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
     return rendered
 
 
-def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = False):
+def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = False, median: bool = False):
     """One frame of `test_tpose` (M:614-629): the human-object network alone over every ray of the frame's box, `_raw2outputs`
     over the frame's background colour, no scene.  `frame` is a `tpose.tpose_frame` batch (the reference's T-pose batch plus the
     `slot` / `count` of `rays.frame_rays_compact`, `time` and `iter_val`).  Under `evaluating(hos)`:
@@ -167,27 +180,37 @@ def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = Fal
       4. `rays.paint_frame` (M:610-612, :627, :629).
     Returns the float frame [H*W,3]; `maps=True` returns a dict `rgb` / `alpha` [H*W] / `depth` [H*W] (`alpha_`, `depth_` of the same
     `_raw2outputs` call, painted over 0).  `want_u8=True` adds the paint kernel's 8-bit frame: a (frame-or-dict, uint8 [H*W,3])
-    pair.  A frame whose camera misses the box (`count == 0`) launches nothing but the paint."""
+    pair.  `median=True` (with `maps=True` only) adds `depth_median` [H*W], the median depth of the human samples' composite
+    (`ops.raw2outputs_median`, the same launch), painted over 0.  A frame whose camera misses the box (`count == 0`) launches nothing
+    but the paint."""
     from . import ops
+    if median and not maps:
+        raise ValueError("render_human_frame(median=True) is one of the maps: pass maps=True as well")
     H, W = int(frame["img_height"]), int(frame["img_width"])
     slot, n = frame["slot"], int(frame["count"])
     dev = slot.device
     bgcolor = frame["bgcolor"]
-    rgb = acc = depth = None
+    rgb = acc = depth = med = None
     if n > 0:
         per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
         per_frame["is_train"] = False
         with evaluating(hos):
             pro = hos.human.frame_prologue(**per_frame)
             out = hos.human(rays=frame["rays"], near=frame["near"], far=frame["far"], prologue=pro, with_cycle=False, **per_frame)
-            rgb, acc, _, depth = ops.raw2outputs(out["human_rgbsigma"], out["z_vals"], out["rays_d"], out["pts_mask"],
-                                                 torch.as_tensor(bgcolor, dtype=torch.float32, device=dev))
+            bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev)
+            if median:
+                m = ops.raw2outputs_median(out["human_rgbsigma"], out["z_vals"], out["rays_d"], out["pts_mask"], bg)
+                rgb, acc, depth, med = m["rgb"], m["acc"], m["depth"], m["depth_median"]
+            else:
+                rgb, acc, _, depth = ops.raw2outputs(out["human_rgbsigma"], out["z_vals"], out["rays_d"], out["pts_mask"], bg)
     rendered, u8 = rays_mod.paint_frame(slot, rgb, bgcolor, H, W, want_u8=want_u8)
     if maps:
         zero = torch.zeros(3, device=dev)
         flat = lambda x: None if x is None else x[:, None].expand(-1, 3)
         rendered = {"rgb": rendered, "alpha": rays_mod.paint_frame(slot, flat(acc), zero, H, W, want_u8=False)[0][:, 0].contiguous(),
                     "depth": rays_mod.paint_frame(slot, flat(depth), zero, H, W, want_u8=False)[0][:, 0].contiguous()}
+        if median:
+            rendered["depth_median"] = rays_mod.paint_frame(slot, flat(med), zero, H, W, want_u8=False)[0][:, 0].contiguous()
     return (rendered, u8) if want_u8 else rendered
 
 

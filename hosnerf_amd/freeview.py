@@ -145,6 +145,20 @@ def save_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W:
     return paths
 
 
+def save_median(out_dir: str, name: str, median, H: int, W: int) -> Dict[str, str]:
+    """Write the median depth of one stage-3 or human-only frame (`eval.render_frame(maps=True, median=True)["depth_median"]`,
+    `eval.render_human_frame(...)`) next to its colour image, under the names stage 1 uses; returns {kind: path}:
+      <name>_depth_median.npy   float32 [H,W], un-normalised, the units of <name>_depth.npy; the last sample's depth where alpha <= 0.5
+      <name>_depth_median.png   its 8-bit preview (`depth_preview`)"""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in ("depth_median.npy", "depth_median.png")}
+    host = np.asarray(median.detach().float().cpu() if isinstance(median, torch.Tensor) else median, dtype=np.float32).reshape(H, W)
+    np.save(paths["depth_median.npy"], host)
+    Image.fromarray(depth_preview(host)).save(paths["depth_median.png"])
+    return paths
+
+
 def save_bkgd_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W: int) -> Dict[str, str]:
     """Write the maps of one stage-1 frame (`eval.render_bkgd_frame(maps=True)`) next to its colour image; returns {kind: path}:
       <name>_depth.npy / <name>_depth_median.npy   float32 [H,W], un-normalised: sum w t_mid and the median distance (stage 1's helper.py:166-190)

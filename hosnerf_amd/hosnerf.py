@@ -72,14 +72,18 @@ class HOSNeRF(nn.Module):
 
     def render(self, batch: Dict[str, torch.Tensor], randomized: bool = True, is_train: bool = True,
                jitters=None, t_rand=None, prologue=None, with_cycle: bool = True, static_cycle: bool = False,
-               maps: bool = False) -> Dict[str, torch.Tensor]:
+               maps: bool = False, median: bool = False) -> Dict[str, torch.Tensor]:
         """M:1507-1596 on one ray batch (keys of SURVEY Appendix B).  Returns the human dict + `rgb` [B,3],
         `idx_fg`, `total_order`, `human_weights_sorted` and the background `ray_history`.
 
         `maps=True` (evaluation only: `is_train=False` under `torch.no_grad()`) adds what the reference's composite returns next
         to the colour, under its key names (M:1615): `alpha` [B] = acc_map, `depth` [B] = depth_map (M:93-94, not divided by
         alpha), and the two premultiplied layers of the merged ray, `rgb_human` [B,3] / `alpha_human` [B] and `rgb_bkg` /
-        `alpha_bkg`, from the same launch that produces `rgb`.  They carry no gradient."""
+        `alpha_bkg`, from the same launch that produces `rgb`.  They carry no gradient.  `median=True` (with `maps=True` only) adds
+        `depth_median` [B], the depth at which the composited ray's cumulative weight crosses 0.5 (`ops.raw2outputs_median`; the
+        last sample's depth where alpha <= 0.5), from that launch too."""
+        if median and not maps:
+            raise ValueError("HOSNeRF.render(median=True) is one of the maps: pass maps=True as well")
         if maps and (is_train or torch.is_grad_enabled()):
             raise ValueError("HOSNeRF.render(maps=True) is an evaluation output: call it with is_train=False under torch.no_grad() "
                              "(depth / opacity carry no gradient; the reference has no loss on them)")
@@ -112,10 +116,13 @@ class HOSNeRF(nn.Module):
         if maps:
             m = ops.merge_composite_maps(
                 last["tdist"], last["rgb"], last["density"], out["human_rgbsigma"], out["newsmpl_pts"], out["pts_mask"],
-                batch["rays_o_bkg"], batch["rays_d_bkg"], batch["newsmpl_to_scale_world"])
+                batch["rays_o_bkg"], batch["rays_d_bkg"], batch["newsmpl_to_scale_world"],
+                want=ops.MAP_KEYS + ((ops.MEDIAN_KEY,) if median else ()))
             out.update(rgb=m["rgb"], idx_fg=m["idx_fg"], total_order=m["total_order"], ray_history=hist,
                        alpha=m["acc"], depth=m["depth"], rgb_human=m["rgb_human"], alpha_human=m["acc_human"],
                        rgb_bkg=m["rgb_bkg"], alpha_bkg=m["acc_bkg"])
+            if median:
+                out["depth_median"] = m["depth_median"]
             return out
         rgb, hw, idx_fg, order, zh = ops.merge_composite(
             last["tdist"], last["rgb"], last["density"], out["human_rgbsigma"], out["newsmpl_pts"], out["pts_mask"],
@@ -135,15 +142,21 @@ class HOSNeRF(nn.Module):
             (main if main is not None else torch.cuda.current_stream(s.device)).wait_stream(s)
 
     def render_bkg_only(self, batch_bkg: Dict[str, torch.Tensor], randomized: bool = False, is_train: bool = False,
-                        jitters=None, maps: bool = False):
+                        jitters=None, maps: bool = False, median: bool = False):
         """Rays that miss the human bounding box (M:818-836, :1434-1452): the last level's 32 samples through the
         NeRF-style composite `_raw2outputs` with an all-ones mask.  Returns rgb [B,3]; with `maps=True` (evaluation only, like
-        `render`) a dict `rgb` [B,3], `alpha` [B], `depth` [B] (`bkg_rgb, bkg_alpha, bkg_depth` of M:835) from that same launch."""
+        `render`) a dict `rgb` [B,3], `alpha` [B], `depth` [B] (`bkg_rgb, bkg_alpha, bkg_depth` of M:835) from that same launch;
+        `median=True` (with `maps=True` only) adds `depth_median` [B] as in `render`, over the 32 background samples."""
+        if median and not maps:
+            raise ValueError("HOSNeRF.render_bkg_only(median=True) is one of the maps: pass maps=True as well")
         if maps and (is_train or torch.is_grad_enabled()):
             raise ValueError("HOSNeRF.render_bkg_only(maps=True) is an evaluation output: is_train=False under torch.no_grad()")
         _, hist = self.model(batch_bkg, 1.0, randomized, is_train, self.near_bkg, self.far_bkg, jitters=jitters)
         last = hist[-1]
         z = last["tdist"][..., :-1].contiguous()
         rgbsigma = torch.cat([last["rgb"], last["density"][..., None]], -1).contiguous()
+        if median:
+            m = ops.raw2outputs_median(rgbsigma, z, batch_bkg["rays_d"], None, None)
+            return {"rgb": m["rgb"], "alpha": m["acc"], "depth": m["depth"], "depth_median": m["depth_median"]}
         rgb, acc, _, depth = ops.raw2outputs(rgbsigma, z, batch_bkg["rays_d"].contiguous(), None, None)
         return {"rgb": rgb, "alpha": acc, "depth": depth} if maps else rgb

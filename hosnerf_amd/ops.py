@@ -1300,6 +1300,23 @@ def raw2outputs(rgbsigma, z_vals, rays_d, mask=None, bgcolor=None, last_dist: fl
                               None if bgcolor is None else bgcolor.contiguous().float(), last_dist)
 
 
+def raw2outputs_median(rgbsigma, z_vals, rays_d, mask=None, bgcolor=None, last_dist: float = 1e10):
+    """`raw2outputs` with the median depth of the ray from the same launch (hos_raw2outputs_median_fwd): a dict `rgb` [B,3], `acc`,
+    `depth`, `depth_median` [B].  `depth_median` is stage 1's `sorted_interp(0.5, integrate_weights(w), t)` on the weights of
+    M:73-92 with the knots t = [z_0 .. z_{S-1}, z_{S-1}]: the depth at which the cumulative weight crosses 0.5, the last sample's
+    depth when it never does (acc <= 0.5), in the units of `depth`.  Forward only: inputs are detached."""
+    det = lambda t: None if t is None else t.detach().contiguous()
+    rgbsigma, z_vals, rays_d, mask = det(rgbsigma), det(z_vals), det(rays_d), det(mask)
+    bgcolor = None if bgcolor is None else det(bgcolor).float()
+    B, S = z_vals.shape
+    dev = z_vals.device
+    out = {"rgb": torch.empty(B, 3, device=dev), "acc": torch.empty(B, device=dev), "depth": torch.empty(B, device=dev),
+           "depth_median": torch.empty(B, device=dev)}
+    call("hos_raw2outputs_median_fwd", ptr(rgbsigma), 4, ptr(rgbsigma) + 12, 4, ptr(z_vals), ptr(rays_d), ptr(mask), ptr(bgcolor),
+         float(last_dist), B, S, ptr(out["rgb"]), ptr(out["acc"]), 0, ptr(out["depth"]), ptr(out["depth_median"]))
+    return out
+
+
 class _MergeComposite(torch.autograd.Function):
     @staticmethod
     def forward(ctx, bkg_rgb, bkg_density, human_rgbsigma, pts_mask, bkg_tdist, pts, rays_o, rays_d, A, tiny_flag, thre_fg):
@@ -1351,6 +1368,7 @@ def merge_composite(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts
 
 
 MAP_KEYS = ("acc", "depth", "rgb_human", "acc_human", "rgb_bkg", "acc_bkg")
+MEDIAN_KEY = "depth_median"                     # on request only: the median instantiation of the merge kernel
 
 
 def merge_composite_maps(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts, pts_mask, rays_o_bkg, rays_d_bkg,
@@ -1359,10 +1377,12 @@ def merge_composite_maps(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmp
     a dict with `rgb` [B,3], `idx_fg` [B] int32, `total_order` [B,Sb+Sh] int32 (bit-identical to `merge_composite`) and, for
     every name in `want`, `acc` / `depth` [B] (acc_map / depth_map of M:93-94, depth not divided by acc), `rgb_human` [B,3] /
     `acc_human` [B] and `rgb_bkg` / `acc_bkg` (premultiplied layers under the merged ray's shared transmittance).
+    `want` may also name `depth_median` [B]: the median depth of the composited samples (see `raw2outputs_median`), still one
+    launch (hos_merge_composite_median_fwd), every other output bit-identical.
     Forward only: inputs are detached and nothing returned here is part of an autograd graph."""
-    unknown = [k for k in want if k not in MAP_KEYS]
+    unknown = [k for k in want if k not in MAP_KEYS + (MEDIAN_KEY,)]
     if unknown:
-        raise ValueError(f"merge_composite_maps: unknown map(s) {unknown}; choose from {MAP_KEYS}")
+        raise ValueError(f"merge_composite_maps: unknown map(s) {unknown}; choose from {MAP_KEYS + (MEDIAN_KEY,)}")
     det = lambda t: t.detach().contiguous()
     rd = det(rays_d_bkg)
     dev = rd.device
@@ -1376,9 +1396,10 @@ def merge_composite_maps(bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmp
         out[k] = torch.empty((B, 3) if k.startswith("rgb") else (B,), device=dev)
     tens = [det(t) for t in (bkg_tdist, bkg_rgb, bkg_density, human_rgbsigma, newsmpl_pts, pts_mask, rays_o_bkg)]
     A = det(newsmpl_to_scale_world).float()
-    call("hos_merge_composite_maps_fwd", *[ptr(t) for t in tens], ptr(rd), ptr(A), ptr(tiny, torch.int32), B, Sb, Sh,
-         float(thre_fg), ptr(out["rgb"]), ptr(out["idx_fg"], torch.int32), ptr(out["total_order"], torch.int32),
-         *[ptr(out.get(k)) for k in MAP_KEYS])
+    median = MEDIAN_KEY in want
+    call("hos_merge_composite_median_fwd" if median else "hos_merge_composite_maps_fwd", *[ptr(t) for t in tens], ptr(rd), ptr(A),
+         ptr(tiny, torch.int32), B, Sb, Sh, float(thre_fg), ptr(out["rgb"]), ptr(out["idx_fg"], torch.int32),
+         ptr(out["total_order"], torch.int32), *[ptr(out.get(k)) for k in MAP_KEYS + ((MEDIAN_KEY,) if median else ())])
     return out
 
 

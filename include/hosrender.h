@@ -518,6 +518,20 @@ int hos_rgbsigma_grad(const float* g_rgbsigma, const float* rgbsigma, int64_t P,
 int hos_raw2outputs_fwd(const float* rgbs, int rgb_ld, const float* sigma, int sigma_ld, const float* z_vals,
                         const float* rays_d, const float* mask, const float* bgcolor, float last_dist,
                         int B, int S, float* rgb, float* acc, float* weights, float* depth, hos_stream_t stream);
+/* hos_raw2outputs_fwd with the median depth of the ray from the same launch (forward only; rgb / acc / weights / depth are
+ * bit-identical to hos_raw2outputs_fwd).  The reference has no median for this composite; the definition is stage 1's
+ * (sorted_interp(0.5, integrate_weights(w), t), stage 1's helper.py:166-190) on the weights w_j of M:73-92 -- after the mask, with the
+ * 1e-10 and last_dist as above -- and the knots t = [z_0 .. z_{S-1}, z_{S-1}]: the unbounded last interval has zero width.
+ *   depth_median [B] = z_k + offset (z_{k+1} - z_k), k the first sample whose cumulative weight exceeds 0.5 (knot 0 of the CDF is 0,
+ *   the knot after sample j < S-1 is min(sum_{i<=j} w_i, 1), after sample S-1 it is 1), offset = clip((0.5 - cw_k) / (cw_{k+1} - cw_k),
+ *   0, 1); z_{S-1} exactly when that sample is the last one or the ray never reaches 0.5 (acc <= 0.5: mask such rays with acc).
+ * Units of depth (M:94), NOT divided by acc.  The cumulative weight of a sample is its lane's base (an exclusive wave scan of the lane
+ * totals, ceil(S/64) consecutive samples per lane) plus the prefix inside the lane; the bin is defined by the FIRST such value above
+ * 0.5 and the value below it is the one that was compared, so the denominator is positive.  depth_median may be NULL. */
+int hos_raw2outputs_median_fwd(const float* rgbs, int rgb_ld, const float* sigma, int sigma_ld, const float* z_vals,
+                               const float* rays_d, const float* mask, const float* bgcolor, float last_dist,
+                               int B, int S, float* rgb, float* acc, float* weights, float* depth, float* depth_median,
+                               hos_stream_t stream);
 /* gradients w.r.t. rgbs / sigma / mask from g_rgb [B,3] (+ optional g_weights [B,S]). */
 int hos_raw2outputs_bwd(const float* g_rgb, const float* g_weights, const float* rgbs, int rgb_ld,
                         const float* sigma, int sigma_ld, const float* z_vals, const float* rays_d,
@@ -555,6 +569,17 @@ int hos_merge_composite_maps_fwd(const float* bkg_tdist, const float* bkg_rgb, c
                                  float* rgb, int32_t* idx_fg, int32_t* total_order,
                                  float* acc, float* depth, float* rgb_human, float* acc_human,
                                  float* rgb_bkg, float* acc_bkg, hos_stream_t stream);
+/* hos_merge_composite_maps_fwd plus the median depth of the composited ray, still ONE launch; every other output is bit-identical.
+ *   depth_median [B]: the median of hos_raw2outputs_median_fwd (M:73-94 weights, stage 1's helper.py:166-190) over the samples the ray
+ *   composites -- the merged sorted order on fg rays (Sb + Sh samples), bkg tdist[:-1] on bg rays (Sb samples) -- with last_dist 1e10.
+ * idx_fg, total_order, each of the six map pointers and depth_median may be NULL.  Sb + Sh <= 256 (HOS_E_SHAPE otherwise). */
+int hos_merge_composite_median_fwd(const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
+                                   const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,
+                                   const float* rays_o_bkg, const float* rays_d_bkg, const float* smpl_to_world,
+                                   const int32_t* tiny_d_flag, int B, int Sb, int Sh, float thre_fg,
+                                   float* rgb, int32_t* idx_fg, int32_t* total_order,
+                                   float* acc, float* depth, float* rgb_human, float* acc_human,
+                                   float* rgb_bkg, float* acc_bkg, float* depth_median, hos_stream_t stream);
 int hos_merge_composite_bwd(const float* g_rgb, const float* g_human_weights_sorted,
                             const float* bkg_tdist, const float* bkg_rgb, const float* bkg_density,
                             const float* human_rgbsigma, const float* newsmpl_pts, const float* pts_mask,

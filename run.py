@@ -10,6 +10,10 @@ binding for the last output of the reference's `test_step`, `test_tpose`, M:591-
 `--render_frames` turn per object state).  Stage 1 (`state_mipnerf360`) with `--scene_dir`: training batches from the scene's unmasked pixels
 (`raybank.RayBank.sample`, the reference's `SingleImageDDPSampler`), `run.run_eval` -> the test split's whole frames under
 <logdir>/render_model + results.json (PSNR), `run.run_render` -> the interpolated camera path under <logdir>/render_video.
+`run.render_maps` writes depth / opacity (stage 3: and human-layer) files next to every frame of run_eval / run_render / run_tpose;
+`run.render_median` (needs `run.render_maps`) adds <name>_depth_median.npy / .png to the stage-3 frames -- the depth at which the
+composited ray's cumulative weight crosses 0.5, the usable depth where the expected depth runs to the far plane -- and changes nothing
+for stage 1, whose maps contain the median already.
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -127,6 +131,8 @@ def run(args, gin):
     model_name = kw.get("model_name")
     if model_name is None:
         raise SystemExit("run.model_name is not bound (pass a --ginc file or --ginb 'run.model_name=\"hosnerf\"')")
+    if bool(kw.get("render_median", False)) and not bool(kw.get("render_maps", False)):
+        raise SystemExit("run.render_median = True requires run.render_maps = True (the median depth is one of the maps)")
     dataset_name = kw.get("dataset_name", "synthetic")
     scene = args.scene_name or "scene"
     exp_name = f"{model_name}_{dataset_name}_{scene}_{str(args.seed).zfill(3)}"          # S3/run.py:108-110
@@ -408,8 +414,9 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     through `eval.render_human_frame`, images under <logdir>/tpose_vis/time_<t>; with several ranks the FRAMES are dealt round-robin
     (no collectives).  Writes <logdir>/results.json."""
     from hosnerf_amd import eval as ev, select_option
-    from hosnerf_amd.freeview import save_image, save_maps
+    from hosnerf_amd.freeview import save_image, save_maps, save_median
     render_maps = bool(kw.get("render_maps", False))          # run.render_maps: depth / opacity / human-layer files next to each frame
+    render_median = bool(kw.get("render_median", False))      # run.render_median: + <name>_depth_median.npy / .png (stage 1: in its maps already)
     if model_name == "state_mipnerf360":
         if run_tpose:
             raise SystemExit("run.run_tpose renders the human-object network (stage 3); stage 1 has run.run_eval / run.run_render")
@@ -435,13 +442,15 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         psnrs = {}
         for i in idxs:
             fr = scene.eval_frame(i, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps)
+            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps, median=render_median)
             frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
             psnrs[fr["frame_name"]] = ev.psnr_metric(rendered, ev.truth_frame(fr))
             if rank == 0:
                 save_image(os.path.join(logdir, "test_vis", fr["frame_name"] + ".png"), rendered, int(fr["img_height"]), int(fr["img_width"]))
                 if render_maps:
                     save_maps(os.path.join(logdir, "test_vis"), fr["frame_name"], frame_maps, int(fr["img_height"]), int(fr["img_width"]))
+                if render_median:
+                    save_median(os.path.join(logdir, "test_vis"), fr["frame_name"], frame_maps["depth_median"], int(fr["img_height"]), int(fr["img_width"]))
         out["test"] = {"psnr": float(sum(psnrs.values()) / len(psnrs)), "frames": psnrs}
         if rank == 0:
             print(f"[run] Test PSNR is {out['test']['psnr']:.4f} over {len(psnrs)} frames")
@@ -452,7 +461,7 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         psnrs = []
         for k in range(count):
             fr = scene.freeview_frame(fidx, k, total, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps)
+            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps, median=render_median)
             frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
             psnrs.append(ev.psnr_metric(rendered, ev.truth_frame(fr)))          # the reference reports it against the training frame too (M:1462)
             if rank == 0:
@@ -461,23 +470,28 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
                 if render_maps:
                     save_maps(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}", frame_maps,
                               int(fr["img_height"]), int(fr["img_width"]))
+                if render_median:
+                    save_median(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}", frame_maps["depth_median"],
+                                int(fr["img_height"]), int(fr["img_width"]))
         out["freeview"] = {"frame_idx": fidx, "frames": count, "of": total, "psnr_vs_training_frame": float(sum(psnrs) / len(psnrs))}
         if rank == 0:
             print(f"[run] Freeview: {count} of {total} cameras about frame {fidx} written to {os.path.join(logdir, 'freeview_vis_newtrans')}")
     if run_tpose:
-        out["tpose"] = render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps)
+        out["tpose"] = render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps, render_median)
     if rank == 0:
         with open(os.path.join(logdir, "results.json"), "w") as f:
             json.dump(out, f, indent=1)
     return {"results": out}
 
 
-def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps: bool):
+def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps: bool, render_median: bool = False):
     """`test_tpose` for every time of `tpose.tpose_times` (M:643-658): `--render_frames` cameras per turn (`--render_limit` stops a
     turn early), rank r renders the frames k % world == r and writes its own files -- <logdir>/tpose_vis/time_{:06}/image-{:05}.jpg
-    (M:631-635) from the paint kernel's 8-bit buffer and, with `run.render_maps`, <name>_alpha.png."""
+    (M:631-635) from the paint kernel's 8-bit buffer and, with `run.render_maps`, <name>_alpha.png; with `run.render_median` also
+    <name>_depth_median.npy / .png (`freeview.save_median`)."""
     from PIL import Image
     from hosnerf_amd import eval as ev, tpose
+    from hosnerf_amd.freeview import save_median
     total = int(args.render_frames)
     count = min(total, args.render_limit) if args.render_limit > 0 else total
     ck = torch.load(ckpt, map_location="cpu", weights_only=False)
@@ -489,13 +503,15 @@ def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, ren
         for k in range(rank, count, world):
             folder, name = tpose.tpose_paths(t, k)
             fr = tpose.tpose_frame(None, None, k, total, bgcolor=bgc, turn=turn, iter_val=step, time=t)
-            rendered, u8 = ev.render_human_frame(hos, fr, maps=render_maps, want_u8=True)
+            rendered, u8 = ev.render_human_frame(hos, fr, maps=render_maps, want_u8=True, median=render_median)
             H, W = int(fr["img_height"]), int(fr["img_width"])
             os.makedirs(os.path.join(logdir, "tpose_vis", folder), exist_ok=True)
             Image.fromarray(u8.view(H, W, 3).cpu().numpy()).save(os.path.join(logdir, "tpose_vis", folder, name))
             if render_maps:
                 alpha8 = ev.to_8b_image(rendered["alpha"].view(H, W)).cpu().numpy()
                 Image.fromarray(alpha8).save(os.path.join(logdir, "tpose_vis", folder, os.path.splitext(name)[0] + "_alpha.png"))
+            if render_median:
+                save_median(os.path.join(logdir, "tpose_vis", folder), os.path.splitext(name)[0], rendered["depth_median"], H, W)
     if rank == 0:
         print(f"[run] T-pose: {count} of {total} cameras for each of {len(times)} states written to {os.path.join(logdir, 'tpose_vis')}")
     return {"times": times, "frames": count, "of": total}
