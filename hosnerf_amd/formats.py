@@ -314,3 +314,64 @@ def skeleton_item(mesh_info: Dict, canonical_joints: np.ndarray, canonical_bbox:
             "motion_weights_priors": approx_gaussian_bone_volumes(canonical_joints, bmin, bmax, volume_size).astype("float32"),
             "dst_posevec": mesh_info["poses"][3:] + 1e-2, "cnl_bbox_min_xyz": bmin, "cnl_bbox_max_xyz": bmax,
             "cnl_bbox_scale_xyz": 2.0 / (bmax - bmin)}
+
+
+# ------------------------------------------------------------------------------------------ meshes (this build's addition)
+def _host_array(x, dtype):
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(x, dtype=dtype)
+
+
+def ply_header(n_vertices: int, n_faces: int, colors: bool) -> bytes:
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(n_vertices)}", "property float x", "property float y", "property float z"]
+    if colors:
+        lines += ["property uchar red", "property uchar green", "property uchar blue"]
+    lines += [f"element face {int(n_faces)}", "property list uchar int vertex_indices", "end_header"]
+    return ("\n".join(lines) + "\n").encode("ascii")
+
+
+def write_ply(path: str, vertices, faces, colors=None):
+    """A triangle mesh as binary little-endian PLY: vertices `float x y z` (+ `uchar red green blue` with `colors` uint8 [V,3]), faces
+    `list uchar int vertex_indices`.  Arrays or tensors; an empty mesh is a valid file."""
+    v = _host_array(vertices, "<f4").reshape(-1, 3)
+    f = _host_array(faces, "<i4").reshape(-1, 3)
+    if colors is None:
+        vrec = v
+    else:
+        c = _host_array(colors, np.uint8).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply: {c.shape[0]} colours for {v.shape[0]} vertices")
+        vrec = np.empty(v.shape[0], dtype=[("p", "<f4", 3), ("c", "u1", 3)])
+        vrec["p"], vrec["c"] = v, c
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", 3)])
+    frec["n"], frec["i"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(ply_header(v.shape[0], f.shape[0], colors is not None))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_ply(path: str):
+    """(vertices float32 [V,3], faces int32 [F,3], colors uint8 [V,3] or None) of a file `write_ply` wrote (that layout only)."""
+    data = open(path, "rb").read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\nformat binary_little_endian 1.0\n") or end < 0:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    head = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    nv = next(int(l.split()[2]) for l in head if l.startswith("element vertex"))
+    nf = next(int(l.split()[2]) for l in head if l.startswith("element face"))
+    colors = "property uchar red" in head
+    if data[:end + len(b"end_header\n")] != ply_header(nv, nf, colors):
+        raise ValueError(f"{path}: a PLY layout other than write_ply's")
+    vdt = np.dtype([("p", "<f4", 3), ("c", "u1", 3)] if colors else [("p", "<f4", 3)])
+    fdt = np.dtype([("n", "u1"), ("i", "<i4", 3)])
+    if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
+        raise ValueError(f"{path}: {len(body)} bytes of data for {nv} vertices and {nf} faces")
+    vrec = np.frombuffer(body, dtype=vdt, count=nv)
+    frec = np.frombuffer(body, dtype=fdt, count=nf, offset=nv * vdt.itemsize)
+    if nf and not (frec["n"] == 3).all():
+        raise ValueError(f"{path}: faces that are not triangles")
+    return (np.ascontiguousarray(vrec["p"]).reshape(nv, 3), np.ascontiguousarray(frec["i"]).reshape(nf, 3),
+            np.ascontiguousarray(vrec["c"]).reshape(nv, 3) if colors else None)

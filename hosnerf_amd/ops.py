@@ -1990,3 +1990,72 @@ def linearp_wgrad(dZ: Planes, X: Planes, dW: torch.Tensor, db, M: int, N: int, K
     _timed(f"gemmp_wgrad[M={N},N={K},K={M}]", 2.0 * M * N * K, lambda: call(
         "hos_linearp_wgrad", _pp(dZ), dZ.ld, _pp(X), X.ld, x_col0,
         ptr(dW) + 4 * w_col0, dW.stride(0), ptr(db), M, N, K, splits, ptr(ws), ws.numel()))
+
+
+# ------------------------------------------------------------------------------------------ canonical mesh (hos_mesh.hip)
+MT_BLOCK = 256          # grid vertices per workgroup of the march kernels (MT_BLOCK of hos_mesh.hip)
+MT_SCAN = 1024          # block counts one pass of the scan workgroup covers (MT_SCAN of hos_mesh.hip)
+
+
+def _grid_args(origin, spacing, dims):
+    """(ox, oy, oz, h, Nx, Ny, Nz) of a grid: `origin` three host floats, `dims` = (Nx, Ny, Nz); everything is rounded to fp32 here,
+    once, so that every launch sees the same grid."""
+    o = np.asarray(origin, dtype=np.float32).reshape(3)
+    Nx, Ny, Nz = (int(d) for d in dims)
+    return float(o[0]), float(o[1]), float(o[2]), float(np.float32(spacing)), Nx, Ny, Nz
+
+
+def grid_points(origin, spacing, dims, first: int, count: int, device="cuda") -> torch.Tensor:
+    """[count,3]: the positions origin + float32(i) * spacing of the grid vertices [first, first + count), linear index
+    (iz*Ny + iy)*Nx + ix."""
+    _lib.require_gpu()
+    pts = torch.empty(int(count), 3, device=device)
+    if count > 0:
+        call("hos_grid_points", *_grid_args(origin, spacing, dims), int(first), int(count), ptr(pts))
+    return pts
+
+
+def grid_alpha(raw, vol, bbox_min, bbox_scale, origin, spacing, dims, first: int, alpha, rgb=None, K: int = 26):
+    """alpha[first + r] = mask * (1 - exp(-raw[r,3] * spacing)) for the vertices `raw` [count,4] was evaluated at (mask: the K-channel
+    sum of the motion-weight volume `vol` [>=K,V,V,V], as `human_sample_warp` under identity transforms), 0 on the grid's outermost
+    layer; rgb[first + r] = raw[r,:3] when given.  `alpha` [Nz,Ny,Nx] and `rgb` [Nz,Ny,Nx,3] are whole-grid tensors, written in place."""
+    count = raw.shape[0]
+    n = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if alpha.numel() != n or (rgb is not None and rgb.numel() != 3 * n) or raw.shape[1] != 4 or vol.shape[0] < K:
+        raise _lib.HosLibraryError(f"grid_alpha: alpha {tuple(alpha.shape)} / rgb / raw {tuple(raw.shape)} / vol {tuple(vol.shape)} do not fit a grid of {tuple(dims)} with K = {K}")
+    if count > 0:
+        call("hos_grid_alpha", ptr(raw), ptr(vol), vol.shape[-1], K, ptr(bbox_min), ptr(bbox_scale), *_grid_args(origin, spacing, dims),
+             int(first), count, ptr(alpha), ptr(rgb))
+    return alpha
+
+
+def march_tets(field, level: float, origin, spacing, rgb=None):
+    """Marching tetrahedra of `field` [Nz,Ny,Nx] at `level` on the grid origin + i * spacing -> (vertices f32 [V,3], colors f32 [V,3]
+    or None, faces int32 [F,3]); `rgb` [Nz,Ny,Nx,3] is interpolated to the vertices.  A closed, consistently oriented surface
+    (normals from inside, field > level, to outside) wherever the field's outermost layer is outside; deterministic order (include/
+    hosrender.h).  Three launches around ONE read-back of (V, F): count + scan, allocate, write.  An empty mesh returns empty tensors
+    without the write launch."""
+    if field.dim() != 3:
+        raise _lib.HosLibraryError(f"march_tets: field must be [Nz,Ny,Nx], got {tuple(field.shape)}")
+    Nz, Ny, Nx = field.shape
+    dev = field.device
+    if rgb is not None and tuple(rgb.shape) != (Nz, Ny, Nx, 3):
+        raise _lib.HosLibraryError(f"march_tets: rgb must be {(Nz, Ny, Nx, 3)}, got {tuple(rgb.shape)}")
+    nblk = _lib.load().hos_march_tets_blocks(Nx, Ny, Nz)
+    _lib.check(min(nblk, 0), "hos_march_tets_blocks")
+    N = Nx * Ny * Nz
+    edge_slot = torch.empty(7 * N, dtype=torch.int32, device=dev)
+    ws = torch.empty(2 * nblk, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    call("hos_march_tets_count", ptr(field), Nx, Ny, Nz, float(level), ptr(edge_slot, torch.int32), ptr(ws, torch.int32), ptr(counts, torch.int32))
+    V, F = (int(c) for c in counts.tolist())              # the one host read-back of the extraction
+    if F >= 2 ** 31 - 1:
+        raise _lib.HosLibraryError("march_tets: 2^31 - 1 or more triangles (a field of noise?); faces are indexed in int32")
+    vertices = torch.empty(V, 3, device=dev)
+    colors = None if rgb is None else torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V > 0 or F > 0:
+        ox, oy, oz, h = _grid_args(origin, spacing, (Nx, Ny, Nz))[:4]
+        call("hos_march_tets_write", ptr(field), ptr(rgb), Nx, Ny, Nz, float(level), ox, oy, oz, h, ptr(edge_slot, torch.int32),
+             ptr(ws, torch.int32), V, F, ptr(vertices), ptr(colors), ptr(faces, torch.int32))
+    return vertices, colors, faces

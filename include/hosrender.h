@@ -870,6 +870,46 @@ int hos_stage1_loss_fwd(const float* rgb, const float* target, int B, const floa
 int hos_stage1_loss_bwd(const float* rgb, const float* target, int B, int Sc, const float* fwd_out4, const float* gout, float m_data,
                         float m_inter, float m_dist, float charb_padding, float* g_rgb, float* g_inter, float* g_dist, hos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Canonical mesh (this build's addition; the reference has no counterpart): the canonical human-object of one object state as an
+ * isosurface of alpha(x) = mask(x) (1 - exp(-sigma(x) h)), the per-sample alpha of `_raw2outputs` (M:73-94) for a sample as
+ * long as a voxel.  The grid: Nx x Ny x Nz vertices, vertex (ix,iy,iz) at origin + (float)i * h per axis (fp32, this one expression
+ * everywhere), linear index (iz*Ny + iy)*Nx + ix, fields [Nz,Ny,Nx].  Every entry: null pointers HOS_E_ARG; a dimension below 2 or
+ * 7 * Nx*Ny*Nz >= 2^31 - 256 HOS_E_SHAPE (edge ids 7 * vertex + family are int32); all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+
+/* pts [count,3] = positions of the vertices [first, first + count) (0 <= first, first + count <= Nx*Ny*Nz; count = 0 launches nothing). */
+int hos_grid_points(float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* pts,
+                    hos_stream_t stream);
+
+/* For the same vertex range: raw [count,4] = (rgb, sigma) of the canonical MLP at hos_grid_points' positions;
+ *   mask  = sum over the first K channels of vol [>=K,V,V,V] of the zero-padded trilinear tap at (x - bbox_min) * bbox_scale - 1 --
+ *           the device function and the expression of hos_human_sample_warp, i.e. its `mask` under identity bone transforms;
+ *   alpha[first + r]   = mask * (1 - exp(-raw[r,3] * h)), and exactly 0 on the outermost vertex layer of the grid (so every surface closes);
+ *   rgb[first + r, :]  = raw[r, :3] when rgb != NULL.
+ * alpha [Nx*Ny*Nz] and rgb [Nx*Ny*Nz,3] are WHOLE-grid arrays.  1 <= K <= 32, V >= 1 (HOS_E_SHAPE otherwise). */
+int hos_grid_alpha(const float* raw, const float* vol, int V, int K, const float* bbox_min, const float* bbox_scale, float ox, float oy,
+                   float oz, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* alpha, float* rgb, hos_stream_t stream);
+
+/* Marching tetrahedra on the 6 Kuhn tetrahedra {c0, c0+e_a, c0+e_a+e_b, c7} of every cell, one per permutation (a,b,c) of the axes
+ * in the order xyz, xzy, yxz, yzx, zxy, zyx (corner bits dx + 2dy + 4dz).  A vertex is inside iff field > level (NaN and == level are
+ * outside).  Every tetrahedron edge runs from a grid vertex v to v + d, d in 1..7 a corner bit mask; v owns it, family d - 1; it carries a
+ * mesh vertex iff exactly one end is inside, at p_v + t (d h), t = (level - f_v) / (f_{v+d} - f_v), t = 0.5 when an end is not finite
+ * or the quotient is not in [0,1]; colours are interpolated with the same t.  Mesh vertices ascend by (owner, family), faces by
+ * (cell, tetrahedron, triangle); normals point from inside to outside.  Nothing depends on scheduling: no atomics.
+ *   hos_march_tets_blocks  number of 256-vertex blocks of the grid (host arithmetic; negative code on a bad shape)
+ *   hos_march_tets_count   two launches: per-block counts + the edge table, then one scan workgroup.  edge_slot int32 [7 Nx*Ny*Nz]:
+ *                          rank of edge (v, family) among its block's mesh vertices, or -1; ws int32 [2 * blocks]: exclusive scans
+ *                          of the blocks' vertex counts, then of their triangle counts; counts int32 [2] = (V, F), read back by the host.
+ *   hos_march_tets_write   one launch: vertices [V,3], colors [V,3] (with rgb [Nx*Ny*Nz,3]; both NULL or neither), faces int32 [F,3],
+ *                          from the edge_slot / ws hos_march_tets_count left.  V and F bound every store.  V = F = 0 launches nothing. */
+int hos_march_tets_blocks(int Nx, int Ny, int Nz);
+int hos_march_tets_count(const float* field, int Nx, int Ny, int Nz, float level, int32_t* edge_slot, int32_t* ws, int32_t* counts,
+                         hos_stream_t stream);
+int hos_march_tets_write(const float* field, const float* rgb, int Nx, int Ny, int Nz, float level, float ox, float oy, float oz, float h,
+                         const int32_t* edge_slot, const int32_t* ws, int V, int F, float* vertices, float* colors, int32_t* faces,
+                         hos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ binding for the last output of the reference's `test_step`, `test_tpose`, M:591-
 `run.render_median` (needs `run.render_maps`) adds <name>_depth_median.npy / .png to the stage-3 frames -- the depth at which the
 composited ray's cumulative weight crosses 0.5, the usable depth where the expected depth runs to the far plane -- and changes nothing
 for stage 1, whose maps contain the median already.
+`run.run_mesh` (stages 2 and 3, with `--scene_dir`; this build's addition) writes the canonical human-object of every object state as
+a triangle mesh, <logdir>/mesh/time_<t>.ply + meshes.json (`hosnerf_amd/mesh.py`; `run.mesh_resolution` 256, `run.mesh_level` 0.5).
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -133,6 +135,8 @@ def run(args, gin):
         raise SystemExit("run.model_name is not bound (pass a --ginc file or --ginb 'run.model_name=\"hosnerf\"')")
     if bool(kw.get("render_median", False)) and not bool(kw.get("render_maps", False)):
         raise SystemExit("run.render_median = True requires run.render_maps = True (the median depth is one of the maps)")
+    if bool(kw.get("run_mesh", False)) and model_name == "state_mipnerf360":
+        raise SystemExit("run.run_mesh extracts the canonical human-object (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
     dataset_name = kw.get("dataset_name", "synthetic")
     scene = args.scene_name or "scene"
     exp_name = f"{model_name}_{dataset_name}_{scene}_{str(args.seed).zfill(3)}"          # S3/run.py:108-110
@@ -318,6 +322,8 @@ def run(args, gin):
     if run_eval or run_render or run_tpose:
         result.update(evaluate_and_render(args, kw, lit, model_name, scene if bank is None else bank, ckpt, logdir, dev, rank, world, run_eval,
                                           run_render, run_tpose, bkgd_chunk=int(gin.get_param("LitData.chunk", 1024 * 32))))
+    if bool(kw.get("run_mesh", False)):
+        result["mesh"] = extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -515,6 +521,42 @@ def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, ren
     if rank == 0:
         print(f"[run] T-pose: {count} of {total} cameras for each of {len(times)} states written to {os.path.join(logdir, 'tpose_vis')}")
     return {"times": times, "frames": count, "of": total}
+
+
+def extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world):
+    """`run.run_mesh` (this build's addition; stage 2 and stage 3): the canonical human-object of every object state as a triangle
+    mesh, from `last.ckpt`, at the times of `tpose.tpose_times` -- `mesh.extract` at `run.mesh_resolution` (256) and `run.mesh_level`
+    (0.5) -> <logdir>/mesh/time_{:06}.ply (binary PLY, per-vertex albedo) and <logdir>/mesh/meshes.json (per time: state, V, F,
+    volume, area, level, spacing, dims).  With several ranks the states are dealt round-robin, each rank writes its own .ply and
+    rank 0 the JSON.  `results.json` is not touched."""
+    from hosnerf_amd import formats, mesh, select_option, tpose
+    from hosnerf_amd.raybank import deal_frames
+    if scene is None:
+        raise SystemExit("run.run_mesh needs --scene_dir (canonical joints and box)")
+    if not os.path.exists(ckpt):
+        raise SystemExit(f"run.run_mesh: {ckpt} does not exist (train first, or pass --ckpt_path)")
+    select_option.load_checkpoint(lit, ckpt, strict=True)
+    resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
+    net = lit.human
+    turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
+    times = tpose.tpose_times(net.transitions_times)
+    os.makedirs(os.path.join(logdir, "mesh"), exist_ok=True)
+    rows = [None] * len(times)
+    for j in deal_frames(len(times), rank, world):
+        m = mesh.extract(net, turn, times[j], resolution=resolution, level=level)
+        formats.write_ply(os.path.join(logdir, "mesh", "time_{:06}.ply".format(times[j])), m["vertices"], m["faces"], m["colors"])
+        rows[j] = {"time": times[j], "state": m["state"], "V": int(m["vertices"].shape[0]), "F": int(m["faces"].shape[0]), "volume": m["volume"],
+                   "area": m["area"], "level": level, "spacing": m["spacing"], "dims": list(m["dims"])}
+    if world > 1:
+        import torch.distributed as dist
+        gathered = [None] * world
+        dist.all_gather_object(gathered, rows)
+        rows = [next(g[j] for g in gathered if g[j] is not None) for j in range(len(times))]
+    if rank == 0:
+        with open(os.path.join(logdir, "mesh", "meshes.json"), "w") as f:
+            json.dump({"time_{:06}".format(r["time"]): r for r in rows}, f, indent=1)
+        print(f"[run] mesh: {len(times)} object states at resolution {resolution}, level {level} written to {os.path.join(logdir, 'mesh')}")
+    return {"times": times, "resolution": resolution, "level": level}
 
 
 def main(argv=None):
