@@ -4,6 +4,10 @@
 //   hos_grid_alpha         alpha = mask * (1 - exp(-sigma h)) of that range into the whole-grid field (M:73-94 `_raw2outputs`: the alpha
 //                          of a sample of length h under the motion-weight mask); mask = the K-channel sum of trilinear_zero, the device
 //                          function and the expression of human_sample_warp_kernel (hos_human.hip) under identity bone transforms
+//   hos_grid_warp          the frame mesh: the backward LBS (N:304-355) of a range of grid vertices of the frame's own box -> x_skel, mask,
+//                          the rows the non-rigid chain and the canonical MLP are evaluated on (the renderer's warp, on a grid)
+//   hos_grid_alpha_masked  hos_grid_alpha with that mask given (one kernel template, two instantiations)
+//   hos_mesh_vertex_normals  per mesh vertex the normalised negative central difference of the trilinear field, spacing h
 //   hos_march_tets_count   marching tetrahedra, count / scan: per 256-vertex block the mesh vertices its grid vertices own and the
 //   hos_march_tets_write   triangles of its cells; one scan workgroup; the write pass at block offsets (as hos_raybank.hip)
 //
@@ -62,22 +66,67 @@ __global__ __launch_bounds__(MT_BLOCK) void grid_points_kernel(MeshGrid g, long 
     pts[r * 3 + 2] = grid_coord(g.oz, iz, g.h);
 }
 
-__global__ __launch_bounds__(MT_BLOCK) void grid_alpha_kernel(const float* __restrict__ raw, const float* __restrict__ vol, int V, int K,
+// The backward LBS of one grid vertex per thread (N:304-355 `_sample_motion_fields`): the observed, body-frame position of the
+// vertex -> x_skel and mask.  The K-loop and the division are lines 51-67 of human_sample_warp_kernel (hos_human.hip), COPIED: moved
+// into a shared header they changed that kernel's instructions (commuted multiplies, inverted branches), so the renderer's kernel
+// stays as it is and tests/test_gpu_frame_mesh.py holds the two bit-equal on the same points.
+__global__ __launch_bounds__(MT_BLOCK) void grid_warp_kernel(const float* __restrict__ R, const float* __restrict__ T,
+                                                             const float* __restrict__ vol, int V, int K,
+                                                             const float* __restrict__ bbox_min, const float* __restrict__ bbox_scale,
+                                                             MeshGrid g, long first, long count, float* __restrict__ x_skel,
+                                                             float* __restrict__ mask) {
+    __shared__ float sR[MT_KMAX * 9], sT[MT_KMAX * 3], sB[6];
+    for (int i = threadIdx.x; i < K * 9; i += blockDim.x) sR[i] = R[i];
+    for (int i = threadIdx.x; i < K * 3; i += blockDim.x) sT[i] = T[i];
+    if (threadIdx.x < 3) { sB[threadIdx.x] = bbox_min[threadIdx.x]; sB[3 + threadIdx.x] = bbox_scale[threadIdx.x]; }
+    __syncthreads();
+    const long p = (long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (p >= count) return;
+    const long u = first + p;
+    const int ix = (int)(u % g.Nx), iy = (int)((u / g.Nx) % g.Ny), iz = (int)(u / ((long)g.Nx * g.Ny));
+    const float px = grid_coord(g.ox, ix, g.h), py = grid_coord(g.oy, iy, g.h), pz = grid_coord(g.oz, iz, g.h);
+    float wsum = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
+    const size_t V3 = (size_t)V * V * V;
+    for (int i = 0; i < K; ++i) {
+        const float* r = sR + i * 9;
+        const float qx = (r[0] * px + r[1] * py + r[2] * pz) + sT[i * 3 + 0];              // N:319
+        const float qy = (r[3] * px + r[4] * py + r[5] * pz) + sT[i * 3 + 1];
+        const float qz = (r[6] * px + r[7] * py + r[8] * pz) + sT[i * 3 + 2];
+        const float gx = (qx - sB[0]) * sB[3] - 1.f, gy = (qy - sB[1]) * sB[4] - 1.f, gz = (qz - sB[2]) * sB[5] - 1.f;
+        const float w = trilinear_zero(vol + i * V3, V, gx, gy, gz);                        // N:322-324
+        wsum += w;
+        ax += w * qx; ay += w * qy; az += w * qz;                                           // N:333-338
+    }
+    const float den = fmaxf(wsum, 1e-4f);                                                   // N:339
+    x_skel[p * 3] = ax / den; x_skel[p * 3 + 1] = ay / den; x_skel[p * 3 + 2] = az / den;
+    mask[p] = wsum;
+}
+
+// MASK_GIVEN = false: hos_grid_alpha, the mask from the volume `vm` [>=K,V,V,V] at the vertex (the canonical mesh);
+// MASK_GIVEN = true:  hos_grid_alpha_masked, the mask read from `vm` [count] (the frame mesh: what grid_warp_kernel wrote).
+template <bool MASK_GIVEN>
+__global__ __launch_bounds__(MT_BLOCK) void grid_alpha_kernel(const float* __restrict__ raw, const float* __restrict__ vm, int V, int K,
                                                               const float* __restrict__ bbox_min, const float* __restrict__ bbox_scale,
                                                               MeshGrid g, long first, long count, float* __restrict__ alpha,
                                                               float* __restrict__ rgb) {
     __shared__ float sB[6];
-    if (threadIdx.x < 3) { sB[threadIdx.x] = bbox_min[threadIdx.x]; sB[3 + threadIdx.x] = bbox_scale[threadIdx.x]; }
-    __syncthreads();
+    if constexpr (!MASK_GIVEN) {
+        if (threadIdx.x < 3) { sB[threadIdx.x] = bbox_min[threadIdx.x]; sB[3 + threadIdx.x] = bbox_scale[threadIdx.x]; }
+        __syncthreads();
+    }
     const long r = (long)blockIdx.x * MT_BLOCK + threadIdx.x;
     if (r >= count) return;
     const long u = first + r;
     const int ix = (int)(u % g.Nx), iy = (int)((u / g.Nx) % g.Ny), iz = (int)(u / ((long)g.Nx * g.Ny));
-    const float qx = grid_coord(g.ox, ix, g.h), qy = grid_coord(g.oy, iy, g.h), qz = grid_coord(g.oz, iz, g.h);
-    const float gx = (qx - sB[0]) * sB[3] - 1.f, gy = (qy - sB[1]) * sB[4] - 1.f, gz = (qz - sB[2]) * sB[5] - 1.f;
     float wsum = 0.f;
-    const size_t V3 = (size_t)V * V * V;
-    for (int i = 0; i < K; ++i) wsum += trilinear_zero(vol + i * V3, V, gx, gy, gz);
+    if constexpr (MASK_GIVEN) {
+        wsum = vm[r];
+    } else {
+        const float qx = grid_coord(g.ox, ix, g.h), qy = grid_coord(g.oy, iy, g.h), qz = grid_coord(g.oz, iz, g.h);
+        const float gx = (qx - sB[0]) * sB[3] - 1.f, gy = (qy - sB[1]) * sB[4] - 1.f, gz = (qz - sB[2]) * sB[5] - 1.f;
+        const size_t V3 = (size_t)V * V * V;
+        for (int i = 0; i < K; ++i) wsum += trilinear_zero(vm + i * V3, V, gx, gy, gz);
+    }
     const float sigma = raw[r * 4 + 3];
     const bool rim = ix == 0 || iy == 0 || iz == 0 || ix == g.Nx - 1 || iy == g.Ny - 1 || iz == g.Nz - 1;
     alpha[u] = rim ? 0.f : wsum * (1.f - expf(-sigma * g.h));        // the outermost layer is outside whatever the network says
@@ -285,6 +334,55 @@ __global__ __launch_bounds__(MT_BLOCK) void march_write_kernel(const float* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------ vertex normals
+// T(p): the trilinear interpolant of the whole-grid field at the position (x,y,z), in grid-index coordinates c = (p - origin) / h,
+// zero outside the grid (a tap that is no grid vertex contributes nothing).  The weights and the tap order are trilinear_zero's; the
+// grid is Nx x Ny x Nz, not cubic, and its coordinates are indices, not [-1,1] -- hence a function of its own.
+__device__ __forceinline__ float trilinear_grid(const float* __restrict__ field, const MeshGrid& g, float x, float y, float z) {
+    const float cx = (x - g.ox) / g.h, cy = (y - g.oy) / g.h, cz = (z - g.oz) / g.h;
+    const float fx = floorf(cx), fy = floorf(cy), fz = floorf(cz);
+    // NaN / huge coordinates: every tap out of range -> 0
+    if (!(fx >= -1.f && fx <= (float)g.Nx && fy >= -1.f && fy <= (float)g.Ny && fz >= -1.f && fz <= (float)g.Nz)) return 0.f;
+    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
+    const float wx1 = cx - fx, wy1 = cy - fy, wz1 = cz - fz;
+    const float wx0 = (fx + 1.f) - cx, wy0 = (fy + 1.f) - cy, wz0 = (fz + 1.f) - cz;
+    float out = 0.f;
+#pragma unroll
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int xi = x0 + dx, yi = y0 + dy, zi = z0 + dz;
+                if (xi >= 0 && xi < g.Nx && yi >= 0 && yi < g.Ny && zi >= 0 && zi < g.Nz) {
+                    const float w = (dx ? wx1 : wx0) * (dy ? wy1 : wy0) * (dz ? wz1 : wz0);
+                    out += field[((long)zi * g.Ny + yi) * g.Nx + xi] * w;
+                }
+            }
+    return out;
+}
+
+// One mesh vertex per thread: g_a = T(v + h e_a) - T(v - h e_a), n = -g / |g| (the field falls from the inside to the outside, so
+// -g points outward, like the faces' orientation); (0,0,0) when g is 0 or not finite.  48 field reads per vertex, all within
+// two cells of the vertex (L1 / L2 hits); no atomics, no adjacency: the result depends on the vertex and the field alone.
+__global__ __launch_bounds__(MT_BLOCK) void vertex_normals_kernel(const float* __restrict__ field, MeshGrid g, const float* __restrict__ vertices,
+                                                                  long V, float* __restrict__ normals) {
+    const long i = (long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (i >= V) return;
+    const float x = vertices[i * 3 + 0], y = vertices[i * 3 + 1], z = vertices[i * 3 + 2];
+    const float gx = trilinear_grid(field, g, x + g.h, y, z) - trilinear_grid(field, g, x - g.h, y, z);
+    const float gy = trilinear_grid(field, g, x, y + g.h, z) - trilinear_grid(field, g, x, y - g.h, z);
+    const float gz = trilinear_grid(field, g, x, y, z + g.h) - trilinear_grid(field, g, x, y, z - g.h);
+    // scaled by the largest component first: the squares of a gradient of 1e-20 (alpha in the tails of the mask) would underflow
+    const float m = fmaxf(fmaxf(fabsf(gx), fabsf(gy)), fabsf(gz));
+    const bool ok = m > 0.f && isfinite(gx) && isfinite(gy) && isfinite(gz);
+    const float sx = gx / m, sy = gy / m, sz = gz / m;
+    const float len = sqrtf((sx * sx + sy * sy) + sz * sz);                       // in [1, sqrt 3]
+    normals[i * 3 + 0] = ok ? (-sx) / len : 0.f;
+    normals[i * 3 + 1] = ok ? (-sy) / len : 0.f;
+    normals[i * 3 + 2] = ok ? (-sz) / len : 0.f;
+}
+
 // HOS_OK and N = Nx*Ny*Nz, or HOS_E_SHAPE: a dimension below 2, or 7 N >= 2^31 - 256 (edge ids 7 u + family are int32)
 int mesh_shape(int Nx, int Ny, int Nz, long* N) {
     if (Nx < 2 || Ny < 2 || Nz < 2) return HOS_E_SHAPE;
@@ -322,8 +420,51 @@ extern "C" int hos_grid_alpha(const float* raw, const float* vol, int V, int K, 
     if (first < 0 || count < 0 || first > N || count > N - first) return HOS_E_ARG;
     if (count == 0) return HOS_OK;
     const MeshGrid g{Nx, Ny, Nz, ox, oy, oz, h};
-    hipLaunchKernelGGL(grid_alpha_kernel, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
+    hipLaunchKernelGGL(grid_alpha_kernel<false>, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
                        static_cast<hipStream_t>(stream), raw, vol, V, K, bbox_min, bbox_scale, g, (long)first, (long)count, alpha, rgb);
+    return hos_launch_status();
+}
+
+extern "C" int hos_grid_warp(const float* R_b, const float* T_b, const float* vol, int V, int K, const float* bbox_min, const float* bbox_scale,
+                             float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* x_skel,
+                             float* mask, hos_stream_t stream) {
+    if (!R_b || !T_b || !vol || !bbox_min || !bbox_scale || !x_skel || !mask) return HOS_E_ARG;
+    long N;
+    if (int e = mesh_shape(Nx, Ny, Nz, &N)) return e;
+    if (V < 1 || K < 1 || K > MT_KMAX) return HOS_E_SHAPE;
+    if (first < 0 || count < 0 || first > N || count > N - first) return HOS_E_ARG;
+    if (count == 0) return HOS_OK;
+    const MeshGrid g{Nx, Ny, Nz, ox, oy, oz, h};
+    hipLaunchKernelGGL(grid_warp_kernel, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), R_b, T_b, vol, V, K, bbox_min, bbox_scale, g, (long)first, (long)count, x_skel, mask);
+    return hos_launch_status();
+}
+
+extern "C" int hos_grid_alpha_masked(const float* raw, const float* mask, float ox, float oy, float oz, float h, int Nx, int Ny, int Nz,
+                                     int64_t first, int64_t count, float* alpha, float* rgb, hos_stream_t stream) {
+    if (!raw || !mask || !alpha) return HOS_E_ARG;
+    long N;
+    if (int e = mesh_shape(Nx, Ny, Nz, &N)) return e;
+    if (first < 0 || count < 0 || first > N || count > N - first) return HOS_E_ARG;
+    if (count == 0) return HOS_OK;
+    const MeshGrid g{Nx, Ny, Nz, ox, oy, oz, h};
+    hipLaunchKernelGGL(grid_alpha_kernel<true>, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), raw, mask, 0, 0, (const float*)nullptr, (const float*)nullptr, g, (long)first,
+                       (long)count, alpha, rgb);
+    return hos_launch_status();
+}
+
+extern "C" int hos_mesh_vertex_normals(const float* field, float ox, float oy, float oz, float h, int Nx, int Ny, int Nz,
+                                       const float* vertices, int64_t V, float* normals, hos_stream_t stream) {
+    if (!field || V < 0) return HOS_E_ARG;
+    long N;
+    if (int e = mesh_shape(Nx, Ny, Nz, &N)) return e;
+    if (V > 7 * N) return HOS_E_SHAPE;                                            // a mesh of this grid has at most 7 vertices per grid vertex
+    if (V == 0) return HOS_OK;                                                   // nothing to launch
+    if (!vertices || !normals) return HOS_E_ARG;
+    const MeshGrid g{Nx, Ny, Nz, ox, oy, oz, h};
+    hipLaunchKernelGGL(vertex_normals_kernel, dim3((unsigned)((V + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), field, g, vertices, (long)V, normals);
     return hos_launch_status();
 }
 

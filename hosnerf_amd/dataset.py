@@ -166,6 +166,28 @@ class SceneItems:
         item.update(frame_name=name, time=float(self.times[idx]), is_train=False, iter_val=torch.full((1,), 1e7))
         return item
 
+    def frame_pose(self, idx: int) -> Dict:
+        """The per-frame dict of frame `idx` WITHOUT any rays (stage 2 and 3; what `mesh.frame_field` / `mesh.extract_frame` take):
+        the pose, the canonical constants and the priors under their `eval.FRAME_KEYS` names (tensors on the device), `time`,
+        `iter_val` = 1e7 and `is_train` = False as `_frame_item` sets them, `frame_name`, `dst_bbox` (the frame's
+        `mesh_infos[name]["bbox"]`: `min_xyz` / `max_xyz` float32 host arrays in the body frame, the box `frame_rays` tests against) and
+        `newsmpl_to_scale_world` = smpl_to_scale_world @ newsmpl_to_smpl (the expression of `eval_frame`: body frame -> the scene's
+        scaled world).  That last key is absent where the scene's cameras hold no `smpl_to_scale_world`."""
+        name = self.frames[idx]
+        dev = self.device
+        Rs, Ts, posevec = self._pose(name)
+        host = {"dst_Rs": Rs, "dst_Ts": Ts, "dst_posevec": posevec, **self._cnl}
+        cam = self.cameras[name]
+        if cam.get("smpl_to_scale_world") is not None:
+            _, _, newsmpl_to_smpl = self._camera(name)
+            host["newsmpl_to_scale_world"] = np.asarray(cam["smpl_to_scale_world"], dtype=np.float64) @ newsmpl_to_smpl
+        item = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in host.items()}
+        item["motion_weights_priors"] = self._prior
+        box = self.mesh_infos[name]["bbox"]
+        item["dst_bbox"] = {"min_xyz": np.asarray(box["min_xyz"], dtype=np.float32), "max_xyz": np.asarray(box["max_xyz"], dtype=np.float32)}
+        item.update(frame_name=name, time=float(self.times[idx]), is_train=False, iter_val=torch.full((1,), 1e7))
+        return item
+
     def eval_frame(self, idx: int, bgcolor=(255.0, 255.0, 255.0)) -> Dict:
         """Frame `idx` seen by its own camera, with the ground-truth pixels (`test_metrics`, model.py:884-1085)."""
         if self.stage != 3:

@@ -323,37 +323,49 @@ def _host_array(x, dtype):
     return np.ascontiguousarray(x, dtype=dtype)
 
 
-def ply_header(n_vertices: int, n_faces: int, colors: bool) -> bytes:
+def ply_header(n_vertices: int, n_faces: int, colors: bool, normals: bool = False) -> bytes:
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(n_vertices)}", "property float x", "property float y", "property float z"]
+    if normals:
+        lines += ["property float nx", "property float ny", "property float nz"]
     if colors:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
     lines += [f"element face {int(n_faces)}", "property list uchar int vertex_indices", "end_header"]
     return ("\n".join(lines) + "\n").encode("ascii")
 
 
-def write_ply(path: str, vertices, faces, colors=None):
-    """A triangle mesh as binary little-endian PLY: vertices `float x y z` (+ `uchar red green blue` with `colors` uint8 [V,3]), faces
-    `list uchar int vertex_indices`.  Arrays or tensors; an empty mesh is a valid file."""
+def _vertex_dtype(colors: bool, normals: bool):
+    return np.dtype([("p", "<f4", 3)] + ([("n", "<f4", 3)] if normals else []) + ([("c", "u1", 3)] if colors else []))
+
+
+def write_ply(path: str, vertices, faces, colors=None, normals=None):
+    """A triangle mesh as binary little-endian PLY: vertices `float x y z` (+ `float nx ny nz` with `normals` float32 [V,3], then
+    + `uchar red green blue` with `colors` uint8 [V,3]), faces `list uchar int vertex_indices`.  Arrays or tensors; an empty mesh is a
+    valid file.  Without normals the file is what it was before normals existed, byte for byte."""
     v = _host_array(vertices, "<f4").reshape(-1, 3)
     f = _host_array(faces, "<i4").reshape(-1, 3)
-    if colors is None:
-        vrec = v
-    else:
+    vrec = np.empty(v.shape[0], dtype=_vertex_dtype(colors is not None, normals is not None))
+    vrec["p"] = v
+    if normals is not None:
+        n = _host_array(normals, "<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply: {n.shape[0]} normals for {v.shape[0]} vertices")
+        vrec["n"] = n
+    if colors is not None:
         c = _host_array(colors, np.uint8).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
             raise ValueError(f"write_ply: {c.shape[0]} colours for {v.shape[0]} vertices")
-        vrec = np.empty(v.shape[0], dtype=[("p", "<f4", 3), ("c", "u1", 3)])
-        vrec["p"], vrec["c"] = v, c
+        vrec["c"] = c
     frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", 3)])
     frec["n"], frec["i"] = 3, f
     with open(path, "wb") as fh:
-        fh.write(ply_header(v.shape[0], f.shape[0], colors is not None))
+        fh.write(ply_header(v.shape[0], f.shape[0], colors is not None, normals is not None))
         fh.write(vrec.tobytes())
         fh.write(frec.tobytes())
 
 
-def read_ply(path: str):
-    """(vertices float32 [V,3], faces int32 [F,3], colors uint8 [V,3] or None) of a file `write_ply` wrote (that layout only)."""
+def read_ply(path: str, with_normals: bool = False):
+    """(vertices float32 [V,3], faces int32 [F,3], colors uint8 [V,3] or None) of a file `write_ply` wrote (that layout only);
+    `with_normals=True` returns a fourth value, the normals float32 [V,3] or None where the file has none."""
     data = open(path, "rb").read()
     end = data.find(b"end_header\n")
     if not data.startswith(b"ply\nformat binary_little_endian 1.0\n") or end < 0:
@@ -362,10 +374,10 @@ def read_ply(path: str):
     body = data[end + len(b"end_header\n"):]
     nv = next(int(l.split()[2]) for l in head if l.startswith("element vertex"))
     nf = next(int(l.split()[2]) for l in head if l.startswith("element face"))
-    colors = "property uchar red" in head
-    if data[:end + len(b"end_header\n")] != ply_header(nv, nf, colors):
+    colors, normals = "property uchar red" in head, "property float nx" in head
+    if data[:end + len(b"end_header\n")] != ply_header(nv, nf, colors, normals):
         raise ValueError(f"{path}: a PLY layout other than write_ply's")
-    vdt = np.dtype([("p", "<f4", 3), ("c", "u1", 3)] if colors else [("p", "<f4", 3)])
+    vdt = _vertex_dtype(colors, normals)
     fdt = np.dtype([("n", "u1"), ("i", "<i4", 3)])
     if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
         raise ValueError(f"{path}: {len(body)} bytes of data for {nv} vertices and {nf} faces")
@@ -373,5 +385,6 @@ def read_ply(path: str):
     frec = np.frombuffer(body, dtype=fdt, count=nf, offset=nv * vdt.itemsize)
     if nf and not (frec["n"] == 3).all():
         raise ValueError(f"{path}: faces that are not triangles")
-    return (np.ascontiguousarray(vrec["p"]).reshape(nv, 3), np.ascontiguousarray(frec["i"]).reshape(nf, 3),
-            np.ascontiguousarray(vrec["c"]).reshape(nv, 3) if colors else None)
+    out = (np.ascontiguousarray(vrec["p"]).reshape(nv, 3), np.ascontiguousarray(frec["i"]).reshape(nf, 3),
+           np.ascontiguousarray(vrec["c"]).reshape(nv, 3) if colors else None)
+    return out + (np.ascontiguousarray(vrec["n"]).reshape(nv, 3) if normals else None,) if with_normals else out

@@ -17,7 +17,30 @@ sample by the non-rigid MLP at `dst_posevec = 1e-2`, the mesh does not.
 Both defaults, level 0.5 and resolution 256, are parameters and have not been measured on a real scene.
 
 The isosurface is marching tetrahedra on the Kuhn split of every cell (hos_mesh.hip): no ambiguous case, so wherever the
-outermost vertex layer is outside -- `hos_grid_alpha` writes 0 there -- the surface is a closed, oriented 2-manifold."""
+outermost vertex layer is outside -- `hos_grid_alpha` writes 0 there -- the surface is a closed, oriented 2-manifold.
+
+The frame mesh (`frame_field`, `extract_frame`): the same subject as it stands in ONE frame -- posed, with that frame's
+pose-dependent deformation, in the body frame of the frame's rays or in the coordinates of the scene.  Take a frame with pose
+(`dst_Rs`, `dst_Ts`, `dst_posevec`), time t and box `mesh_infos[name]["bbox"]`: the body frame of the item's `rays`, the space
+`frame_rays` tests against.  With pro = `net.frame_prologue(...)` at `is_train=False` and `iter_val=1e7` (as the evaluation frames
+of `dataset.SceneItems`), for a body-frame point p of `grid_of_box(bbox.min, bbox.max, resolution)` (spacing h):
+
+    (x_skel, mask) = backward LBS of p         # N:304-355, the K-loop of human_sample_warp_kernel on pro["R_b"], pro["T_b"], pro["vol"]
+    cnl            = net._nonrigid_fwd(net._nr, x_skel, pro["cond"], pro["band_w"], save=False)[0]
+    raw            = net._canonical_fwd(cnl, pro["state"], save=False)[0]
+    alpha(p)       = 0 on the outermost vertex layer, else mask * (1 - exp(-raw[3] * h));   colour raw[:3]
+
+and alpha(p) = 0 as well on a vertex layer past the box (`grid_of_box` rounds an extent up to whole voxels, so a shorter axis can
+have one; `clip_to_box`): the renderer's rays are cut to the box, and every mesh vertex then lies within the box grown by h.  This is
+the masked alpha of `_raw2outputs` (M:73-94) for a sample of length h at p: what `render_human_frame` and the stage-3 merge
+composite for that frame.  The field is taken THROUGH THE BACKWARD WARP, the one the renderer samples; canonical vertices pushed
+forward by `lbs_forward` would follow the approximate inverse the cycle loss trains and would not sit where the rendered pixels are.
+The canonical mesh is the special case of identity transforms and no non-rigid offset.  Level 0.5 and resolution 256 are the same
+parameters, as unmeasured on a real scene as they are for the canonical mesh.  Each frame is marched on its own: there is no vertex
+correspondence between frames.
+
+Normals (`normals=True`, both meshes): per vertex the normalised negative central difference, step h, of the field's trilinear
+interpolant (`ops.mesh_vertex_normals`), so they follow the field the surface was cut from and need no face adjacency."""
 from __future__ import annotations
 
 import math
@@ -27,7 +50,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .eval import evaluating
+from .eval import FRAME_KEYS, evaluating
 from .mipnerf360 import select_state
 
 THIN_ROWS = 16384            # from this many rows on the canonical MLP runs on the thin kernels (ops.thin_dgrad_rows)
@@ -95,14 +118,132 @@ def mesh_measures(vertices: torch.Tensor, faces: torch.Tensor):
     return float(volume), float(area)
 
 
-def extract(net, turn, time: float, resolution: int = 256, level: float = 0.5, chunk: int = 1 << 18) -> Dict:
+def extract(net, turn, time: float, resolution: int = 256, level: float = 0.5, chunk: int = 1 << 18, normals: bool = False) -> Dict:
     """The mesh of the canonical human-object at `time`'s object state: `canonical_field` on `turn` (a `tpose.TposeTurn`: canonical
     box, joints and priors), then `ops.march_tets` at `level`.  Returns `vertices` f32 [V,3], `faces` int32 [F,3] and `colors` uint8
     [V,3] (the 8-bit truncation of `to_8b_image`) on the device, `origin`, `spacing`, `dims`, `state`, the signed `volume` and
-    the `area` as floats, and the field it was extracted from (`alpha` [Nz,Ny,Nx], `rgb` [Nz,Ny,Nx,3]).  `level` and `resolution` are unmeasured defaults (module docstring)."""
+    the `area` as floats, and the field it was extracted from (`alpha` [Nz,Ny,Nx], `rgb` [Nz,Ny,Nx,3]).  `level` and `resolution` are unmeasured defaults (module docstring).
+    `normals=True` adds `normals` f32 [V,3] (`ops.mesh_vertex_normals`; `None` otherwise); nothing else changes."""
     field = canonical_field(net, turn.const, time, resolution, chunk)
     vertices, colors, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"], rgb=field["rgb"])
     volume, area = mesh_measures(vertices, faces)
     return {"vertices": vertices, "faces": faces, "colors": (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
             "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
-            "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"]}
+            "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"],
+            "normals": ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None}
+
+
+# ------------------------------------------------------------------------------------------ the frame mesh
+SPACES = ("world", "body")
+
+
+def layers_in_box(origin, spacing, dims, bmax):
+    """Per axis the index of the first vertex layer BEYOND the box: `grid_of_box` rounds an extent that is no multiple of the spacing
+    up, so on such an axis the last layer before the rim lies past `bmax` (by less than one spacing; a layer within 1e-4 spacings of
+    `bmax` counts as on it, the tolerance of `grid_of_box`).  Positions are `grid_coord`'s: origin + float32(i) * spacing in fp32."""
+    h = np.float32(spacing)
+    o, hi = np.asarray(origin, dtype=np.float32).reshape(3), np.asarray(bmax, dtype=np.float32).reshape(3)
+    out = []
+    for a in range(3):
+        c = (o[a] + np.arange(int(dims[a]), dtype=np.float32) * h).astype(np.float64)
+        out.append(int(np.searchsorted(c, float(hi[a]) + 1e-4 * float(h), side="right")))
+    return tuple(out)
+
+
+def clip_to_box(alpha: torch.Tensor, origin, spacing, dims, bmax) -> torch.Tensor:
+    """alpha [Nz,Ny,Nx] := +0 on every vertex layer beyond the box (`layers_in_box`), in place.  The renderer's rays are cut to the
+    frame's box (`rays_intersect_3d_bbox`), so whatever the network says past it is never composited; and every mesh vertex then lies
+    within the box grown by one spacing."""
+    kx, ky, kz = layers_in_box(origin, spacing, dims, bmax)
+    alpha[:, :, kx:] = 0.0
+    alpha[:, ky:] = 0.0
+    alpha[kz:] = 0.0
+    return alpha
+
+
+def frame_field(net, pose: Dict, resolution: int = 256, chunk: int = 1 << 18) -> Dict:
+    """alpha [Nz,Ny,Nx] and rgb [Nz,Ny,Nx,3] of `net` (stage 2 or 3) on `grid_of_box` of the FRAME's box `pose["dst_bbox"]`
+    (`min_xyz` / `max_xyz`, body frame), through the backward warp of the frame (module docstring).  `pose` is
+    `dataset.SceneItems.frame_pose(idx)`: the per-frame keys of `eval.FRAME_KEYS` plus `dst_bbox`; `is_train` is False here whatever
+    it holds, `iter_val` 1e7 unless given.  Under `evaluating`, `no_grad` and `ops.guarded_forward`; one `frame_prologue` per call,
+    then per chunk of `chunk` >= 16384 vertices (the last one moved back, as `canonical_field`) `ops.grid_warp`, the non-rigid chain,
+    the canonical MLP and `ops.grid_alpha_masked`; at the end `clip_to_box`: alpha is 0 on the layers past the box, as on the rim."""
+    chunk = int(chunk)
+    if chunk < THIN_ROWS:
+        raise ValueError(f"frame_field: chunk {chunk} < {THIN_ROWS} rows (the thin kernels' lower bound)")
+    bmin, bscale = pose["cnl_bbox_min_xyz"].contiguous(), pose["cnl_bbox_scale_xyz"].contiguous()
+    dev = bmin.device
+    box = pose["dst_bbox"]
+    grid = grid_of_box(np.asarray(box["min_xyz"], dtype=np.float32), np.asarray(box["max_xyz"], dtype=np.float32), resolution)
+    origin, h, dims = grid["origin"], grid["spacing"], grid["dims"]
+    Nx, Ny, Nz = dims
+    N = Nx * Ny * Nz
+    per_frame = {k: pose[k] for k in FRAME_KEYS if k in pose}
+    per_frame["is_train"] = False
+    per_frame.setdefault("iter_val", 1e7)
+    K = int(net.cfg.total_bones)
+    alpha = torch.empty(Nz, Ny, Nx, device=dev)
+    rgb = torch.empty(Nz, Ny, Nx, 3, device=dev)
+    found = {}
+
+    def run():
+        pro = net.frame_prologue(**per_frame)                                                # once per call
+        found["state"] = pro["state"]
+        rows = min(chunk, N)
+        for c0 in range(0, N, rows):
+            first = min(c0, N - rows)
+            x_skel, mask = ops.grid_warp(pro["R_b"], pro["T_b"], pro["vol"], bmin, bscale, origin, h, dims, first, rows, K=K)
+            cnl, _ = net._nonrigid_fwd(net._nr, x_skel, pro["cond"], pro["band_w"], save=False)
+            raw, _ = net._canonical_fwd(cnl, pro["state"], save=False)
+            ops.grid_alpha_masked(raw, mask, origin, h, dims, first, alpha, rgb)
+        clip_to_box(alpha, origin, h, dims, box["max_xyz"])
+
+    with evaluating(net):
+        ops.guarded_forward(net, dev, run)
+    return {"alpha": alpha, "rgb": rgb, "origin": origin, "spacing": h, "dims": dims, "state": found["state"]}
+
+
+def to_space(vertices: torch.Tensor, faces: torch.Tensor, normals, A) -> tuple:
+    """A mesh under the affine map `A` [4,4]: v' = A[:3,:3] v + A[:3,3], evaluated in float64 and rounded once; normals turned by the
+    linear part and renormalised (a zero normal stays zero) -- exact for a similarity, mirrored or not; where det A[:3,:3] < 0 two
+    indices of every face are swapped, so that the orientation stays outward.  -> (vertices, faces, normals)."""
+    A = torch.as_tensor(np.asarray(A, dtype=np.float64), device=vertices.device)
+    L, t = A[:3, :3], A[:3, 3]
+    v = (vertices.double() @ L.T + t).float()
+    if normals is not None:
+        n = normals.double() @ L.T
+        length = n.norm(dim=1, keepdim=True)
+        normals = torch.where(length > 0, n / length.clamp_min(1e-300), torch.zeros_like(n)).float()
+    if float(torch.linalg.det(L)) < 0:
+        faces = faces[:, [0, 2, 1]].contiguous()
+    return v, faces, normals
+
+
+def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, space: str = "world", normals: bool = False,
+                  chunk: int = 1 << 18) -> Dict:
+    """The mesh of the human-object as it stands in the frame of `pose` (`dataset.SceneItems.frame_pose`): `frame_field`, then
+    `ops.march_tets` at `level`.  Returns what `extract` returns (`origin`, `spacing`, `dims` and the field `alpha` / `rgb` are the
+    body-frame grid's) plus `space`, `to_world` (float32 [4,4] host array: `pose["newsmpl_to_scale_world"]`, the body frame -> the
+    scene's scaled world; the identity for `space="body"`), `normals` (f32 [V,3] or None), `frame_name` and `time`.
+    `space="world"` writes the vertices (and turns the normals) by `to_space`; `volume` and `area` are those of the returned
+    vertices.  `level` and `resolution` are unmeasured defaults (module docstring)."""
+    if space not in SPACES:
+        raise ValueError(f"extract_frame: space {space!r} is not one of {SPACES}")
+    to_world = np.eye(4, dtype=np.float32)
+    if space == "world":
+        if pose.get("newsmpl_to_scale_world") is None:
+            raise ValueError("extract_frame: space=\"world\" needs pose[\"newsmpl_to_scale_world\"], which this scene's cameras do not "
+                             "give (no `smpl_to_scale_world`); use space=\"body\"")
+        A = pose["newsmpl_to_scale_world"]
+        to_world = np.ascontiguousarray(A.detach().cpu().numpy() if hasattr(A, "detach") else A, dtype=np.float32).reshape(4, 4)
+    field = frame_field(net, pose, resolution, chunk)
+    vertices, colors, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"], rgb=field["rgb"])
+    vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None
+    if space == "world":
+        vertices, faces, vn = to_space(vertices, faces, vn, to_world)
+    volume, area = mesh_measures(vertices, faces)
+    time = pose.get("time")
+    return {"vertices": vertices, "faces": faces, "colors": (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
+            "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
+            "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"], "normals": vn, "space": space, "to_world": to_world,
+            "frame_name": pose.get("frame_name"), "time": None if time is None else float(time)}

@@ -2029,6 +2029,48 @@ def grid_alpha(raw, vol, bbox_min, bbox_scale, origin, spacing, dims, first: int
     return alpha
 
 
+def grid_warp(R_b, T_b, vol, bbox_min, bbox_scale, origin, spacing, dims, first: int, count: int, K: int = 26):
+    """(x_skel [count,3], mask [count]): the backward LBS of the grid vertices [first, first + count) of a grid in a frame's body
+    space -- `human_sample_warp`'s `x_skel` / `mask` for those positions, bit for bit.  `R_b` [K,3,3] / `T_b` [K,3] the frame's backward
+    bone transforms, `vol` [>=K,V,V,V] its motion-weight volume, `bbox_min` / `bbox_scale` of the canonical box."""
+    _lib.require_gpu()
+    if tuple(R_b.shape) != (K, 3, 3) or tuple(T_b.shape) != (K, 3) or vol.dim() != 4 or vol.shape[0] < K:
+        raise _lib.HosLibraryError(f"grid_warp: R_b {tuple(R_b.shape)} / T_b {tuple(T_b.shape)} / vol {tuple(vol.shape)} do not fit K = {K}")
+    dev = vol.device
+    x_skel, mask = torch.empty(int(count), 3, device=dev), torch.empty(int(count), device=dev)
+    if count > 0:
+        call("hos_grid_warp", ptr(R_b), ptr(T_b), ptr(vol), vol.shape[-1], K, ptr(bbox_min), ptr(bbox_scale), *_grid_args(origin, spacing, dims),
+             int(first), int(count), ptr(x_skel), ptr(mask))
+    return x_skel, mask
+
+
+def grid_alpha_masked(raw, mask, origin, spacing, dims, first: int, alpha, rgb=None):
+    """`grid_alpha` with the mask given: alpha[first + r] = mask[r] * (1 - exp(-raw[r,3] * spacing)), 0 on the grid's outermost layer;
+    rgb[first + r] = raw[r,:3] when given.  `raw` [count,4], `mask` [count] (of `grid_warp`); `alpha` / `rgb` are whole-grid tensors."""
+    count = raw.shape[0]
+    n = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if alpha.numel() != n or (rgb is not None and rgb.numel() != 3 * n) or raw.shape[1] != 4 or mask.numel() != count:
+        raise _lib.HosLibraryError(f"grid_alpha_masked: alpha {tuple(alpha.shape)} / rgb / raw {tuple(raw.shape)} / mask {tuple(mask.shape)} do not fit a grid of {tuple(dims)}")
+    if count > 0:
+        call("hos_grid_alpha_masked", ptr(raw), ptr(mask), *_grid_args(origin, spacing, dims), int(first), count, ptr(alpha), ptr(rgb))
+    return alpha
+
+
+def mesh_vertex_normals(field, origin, spacing, vertices) -> torch.Tensor:
+    """normals [V,3] of the mesh `vertices` [V,3] `march_tets` extracted from `field` [Nz,Ny,Nx]: the normalised negative central
+    difference (step `spacing`) of the field's trilinear interpolant, pointing from inside to outside; exact zeros where the difference
+    vanishes (include/hosrender.h)."""
+    if field.dim() != 3 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.HosLibraryError(f"mesh_vertex_normals: field must be [Nz,Ny,Nx] and vertices [V,3], got {tuple(field.shape)} / {tuple(vertices.shape)}")
+    _lib.require_gpu()
+    Nz, Ny, Nx = field.shape
+    V = vertices.shape[0]
+    normals = torch.empty(V, 3, device=field.device)
+    if V > 0:
+        call("hos_mesh_vertex_normals", ptr(field), *_grid_args(origin, spacing, (Nx, Ny, Nz)), ptr(vertices), V, ptr(normals))
+    return normals
+
+
 def march_tets(field, level: float, origin, spacing, rgb=None):
     """Marching tetrahedra of `field` [Nz,Ny,Nx] at `level` on the grid origin + i * spacing -> (vertices f32 [V,3], colors f32 [V,3]
     or None, faces int32 [F,3]); `rgb` [Nz,Ny,Nx,3] is interpolated to the vertices.  A closed, consistently oriented surface

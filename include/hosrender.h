@@ -891,6 +891,31 @@ int hos_grid_points(float ox, float oy, float oz, float h, int Nx, int Ny, int N
 int hos_grid_alpha(const float* raw, const float* vol, int V, int K, const float* bbox_min, const float* bbox_scale, float ox, float oy,
                    float oz, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* alpha, float* rgb, hos_stream_t stream);
 
+/* The frame mesh: the same field on a grid over the FRAME's box (body frame, the space of the frame's rays), through the renderer's
+ * backward warp.  For the vertices [first, first + count): p = the vertex position (hos_grid_points' expression);
+ *   x_skel [count,3], mask [count] = the backward LBS of p (N:304-355 `_sample_motion_fields`, N:319-339: q_i = R_b[i] p + T_b[i],
+ *   w_i = zero-padded trilinear tap of vol channel i at (q_i - bbox_min) * bbox_scale - 1, mask = sum w_i,
+ *   x_skel = sum w_i q_i / max(mask, 1e-4)) -- the arithmetic of hos_human_sample_warp on the same points, bit for bit.
+ * R_b [K,3,3], T_b [K,3], vol [>=K,V,V,V]; bbox_min / bbox_scale [3] of the CANONICAL box.  1 <= K <= 32, V >= 1 (HOS_E_SHAPE
+ * otherwise); a range outside the grid HOS_E_ARG; count = 0 launches nothing. */
+int hos_grid_warp(const float* R_b, const float* T_b, const float* vol, int V, int K, const float* bbox_min, const float* bbox_scale,
+                  float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* x_skel, float* mask,
+                  hos_stream_t stream);
+
+/* hos_grid_alpha with the mask given: alpha[first + r] = mask[r] * (1 - exp(-raw[r,3] * h)), exactly 0 on the outermost vertex layer;
+ * rgb[first + r, :] = raw[r, :3] when rgb != NULL.  raw [count,4], mask [count] (what hos_grid_warp wrote for the range). */
+int hos_grid_alpha_masked(const float* raw, const float* mask, float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, int64_t first,
+                          int64_t count, float* alpha, float* rgb, hos_stream_t stream);
+
+/* normals [V,3] of mesh vertices [V,3] from the whole-grid field [Nz,Ny,Nx] they were extracted from:
+ *   g_a = T(v + h e_a) - T(v - h e_a), a = x, y, z;   n = -g / |g|, and (0,0,0) where g is 0 or not finite.  |g| is taken of
+ *   s = g / max_a |g_a| (n = -s / |s|), so that a gradient of any magnitude, 1e-20 in the tails of the mask included, gives a unit normal.
+ * T(p) is the trilinear interpolant of the field in grid-index coordinates c = (p - origin) / h, taps outside the grid zero.  The
+ * field falls from inside to outside, so n points outward, as the faces' orientation.  One thread per vertex, no atomics.
+ * V = 0 launches nothing; V > 7 Nx*Ny*Nz (more than any mesh of this grid) HOS_E_SHAPE. */
+int hos_mesh_vertex_normals(const float* field, float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, const float* vertices,
+                            int64_t V, float* normals, hos_stream_t stream);
+
 /* Marching tetrahedra on the 6 Kuhn tetrahedra {c0, c0+e_a, c0+e_a+e_b, c7} of every cell, one per permutation (a,b,c) of the axes
  * in the order xyz, xzy, yxz, yzx, zxy, zyx (corner bits dx + 2dy + 4dz).  A vertex is inside iff field > level (NaN and == level are
  * outside).  Every tetrahedron edge runs from a grid vertex v to v + d, d in 1..7 a corner bit mask; v owns it, family d - 1; it carries a

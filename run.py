@@ -16,6 +16,9 @@ composited ray's cumulative weight crosses 0.5, the usable depth where the expec
 for stage 1, whose maps contain the median already.
 `run.run_mesh` (stages 2 and 3, with `--scene_dir`; this build's addition) writes the canonical human-object of every object state as
 a triangle mesh, <logdir>/mesh/time_<t>.ply + meshes.json (`hosnerf_amd/mesh.py`; `run.mesh_resolution` 256, `run.mesh_level` 0.5).
+`run.run_mesh_frames` (same stages, same two parameters; this build's addition) writes the POSED human-object of each frame that
+`run.run_eval` would choose (`--eval_skip`), through the renderer's backward warp and in the scene's coordinates,
+<logdir>/mesh_frames/<frame_name>.ply + meshes.json (`mesh.extract_frame`; `run.mesh_space` "world" | "body", `run.mesh_normals` True).
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -137,6 +140,10 @@ def run(args, gin):
         raise SystemExit("run.render_median = True requires run.render_maps = True (the median depth is one of the maps)")
     if bool(kw.get("run_mesh", False)) and model_name == "state_mipnerf360":
         raise SystemExit("run.run_mesh extracts the canonical human-object (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
+    if bool(kw.get("run_mesh_frames", False)) and model_name == "state_mipnerf360":
+        raise SystemExit("run.run_mesh_frames extracts the posed human-object of each frame (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
+    if bool(kw.get("run_mesh_frames", False)) and str(kw.get("mesh_space", "world")) not in ("world", "body"):
+        raise SystemExit(f"run.mesh_space = {kw.get('mesh_space')!r}: \"world\" (the scene's coordinates) or \"body\" (the frame's body frame)")
     dataset_name = kw.get("dataset_name", "synthetic")
     scene = args.scene_name or "scene"
     exp_name = f"{model_name}_{dataset_name}_{scene}_{str(args.seed).zfill(3)}"          # S3/run.py:108-110
@@ -324,6 +331,8 @@ def run(args, gin):
                                           run_render, run_tpose, bkgd_chunk=int(gin.get_param("LitData.chunk", 1024 * 32))))
     if bool(kw.get("run_mesh", False)):
         result["mesh"] = extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world)
+    if bool(kw.get("run_mesh_frames", False)):
+        result["mesh_frames"] = extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -444,7 +453,7 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     out = {}
     if run_eval:
         n = len(scene)
-        idxs = list(range(0, n, args.eval_skip)) if args.eval_skip > 0 else sorted({int(round(i * (n - 1) / 7.0)) for i in range(8)} if n > 1 else {0})
+        idxs = eval_frame_indices(n, args.eval_skip)
         psnrs = {}
         for i in idxs:
             fr = scene.eval_frame(i, bgcolor=bgc)
@@ -557,6 +566,53 @@ def extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world):
             json.dump({"time_{:06}".format(r["time"]): r for r in rows}, f, indent=1)
         print(f"[run] mesh: {len(times)} object states at resolution {resolution}, level {level} written to {os.path.join(logdir, 'mesh')}")
     return {"times": times, "resolution": resolution, "level": level}
+
+
+def eval_frame_indices(n: int, eval_skip: int):
+    """The frames `run.run_eval` renders: every `--eval_skip`-th, else eight spread over the sequence."""
+    return list(range(0, n, eval_skip)) if eval_skip > 0 else sorted({int(round(i * (n - 1) / 7.0)) for i in range(8)} if n > 1 else {0})
+
+
+def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
+    """`run.run_mesh_frames` (this build's addition; stage 2 and stage 3): the human-object as it stands in each chosen frame --
+    posed, with the frame's non-rigid offset, through the renderer's backward warp (`mesh.extract_frame`) -- from `last.ckpt`, for the
+    frames `run.run_eval` chooses (`--eval_skip`, else eight over the sequence), at `run.mesh_resolution` (256) and `run.mesh_level`
+    (0.5), in `run.mesh_space` ("world": the scene's scaled world, or "body"), with per-vertex normals unless `run.mesh_normals =
+    False` -> <logdir>/mesh_frames/<frame_name>.ply and <logdir>/mesh_frames/meshes.json (per frame: time, state, V, F, volume, area,
+    level, spacing, dims, space, to_world).  With several ranks the frames are dealt round-robin, each rank writes its own .ply and
+    rank 0 the JSON.  `results.json` is not touched."""
+    from hosnerf_amd import formats, mesh, select_option
+    from hosnerf_amd.raybank import deal_frames
+    if scene is None:
+        raise SystemExit("run.run_mesh_frames needs --scene_dir (the frames' poses, boxes and cameras)")
+    if not os.path.exists(ckpt):
+        raise SystemExit(f"run.run_mesh_frames: {ckpt} does not exist (train first, or pass --ckpt_path)")
+    select_option.load_checkpoint(lit, ckpt, strict=True)
+    resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
+    space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
+    net = lit.human
+    idxs = eval_frame_indices(len(scene), args.eval_skip)
+    os.makedirs(os.path.join(logdir, "mesh_frames"), exist_ok=True)
+    rows = [None] * len(idxs)
+    for j in deal_frames(len(idxs), rank, world):
+        try:
+            m = mesh.extract_frame(net, scene.frame_pose(idxs[j]), resolution=resolution, level=level, space=space, normals=normals)
+        except ValueError as e:                      # cameras without smpl_to_scale_world: say so and stop, no half-written sequence
+            raise SystemExit(f"run.run_mesh_frames: {e}")
+        formats.write_ply(os.path.join(logdir, "mesh_frames", m["frame_name"] + ".ply"), m["vertices"], m["faces"], m["colors"], m["normals"])
+        rows[j] = {"frame_name": m["frame_name"], "time": m["time"], "state": m["state"], "V": int(m["vertices"].shape[0]),
+                   "F": int(m["faces"].shape[0]), "volume": m["volume"], "area": m["area"], "level": level, "spacing": m["spacing"],
+                   "dims": list(m["dims"]), "space": space, "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+    if world > 1:
+        import torch.distributed as dist
+        gathered = [None] * world
+        dist.all_gather_object(gathered, rows)
+        rows = [next(g[j] for g in gathered if g[j] is not None) for j in range(len(idxs))]
+    if rank == 0:
+        with open(os.path.join(logdir, "mesh_frames", "meshes.json"), "w") as f:
+            json.dump({r["frame_name"]: r for r in rows}, f, indent=1)
+        print(f"[run] frame meshes: {len(idxs)} frames at resolution {resolution}, level {level}, space {space} written to {os.path.join(logdir, 'mesh_frames')}")
+    return {"frames": [r["frame_name"] for r in rows], "resolution": resolution, "level": level, "space": space}
 
 
 def main(argv=None):
