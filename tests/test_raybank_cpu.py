@@ -108,10 +108,6 @@ def test_launcher_plumbing_run_with_scene_dir(tmp_path):
     plan = launcher.main(["--ginc", gin, "--scene_name", "Backpack", "--logbase", str(tmp_path / "logs"), "--cpu", "--scene_dir", scene,
                           "--ginb", "run.max_steps=3", "--ginb", "run.run_eval=True", "--ginb", "run.run_render=True"])
     assert plan["mode"] == "cpu-plumbing" and plan["model_name"] == "state_mipnerf360" and plan["checkpoint_roundtrip"] == {"missing": 0, "unexpected": 0}
-    src = inspect.getsource(launcher.run)
-    assert "stage 1 takes --items or synthetic rays" not in src and "bank.sample(" in src
-    ev_src = inspect.getsource(launcher.evaluate_and_render)
-    assert "stage 2 reports its training loss only" in ev_src                                  # stage 2 keeps its refusal
     assert inspect.signature(launcher.evaluate_and_render).parameters["run_tpose"].default is False
 
 
