@@ -7,6 +7,9 @@
 // In the reference this is ~40 torch launches with [B,S,3,3] / [B,S,12,21] temporaries and a
 // vmap(jacrev) autograd pass (13.5 % + 18 % of its forward time).
 //
+// hos_encode_ipe_points: the same rows for Gaussians given directly (mean pts[p], covariance var I: the background mesh's grid
+// vertices, hosnerf_amd/mesh.py) -- the same kernel with another first stage (PointStage below), the reference's forward(means, covs).
+//
 // HBM-bound on the write of X: algorithmic bytes/sample = 4*ldx written + 4 read (tdist).
 // Built with -ffp-contract=off: sin(x*2^l + pi/2) must round the sum in fp32 exactly like the
 // reference does (for 2^11*x ~ 4096 the fp32 ulp is 4.9e-4 -- a fused or cosf() variant differs
@@ -75,31 +78,36 @@ template <typename E> __device__ __forceinline__ void split_store2(unsigned shor
 }
 __device__ __forceinline__ size_t plane_off(long row, int c, int ld) { return (size_t)row * (2 * ld) + (c >> 5) * 64 + (c & 31); }
 
-// PLANES = false: X fp32 [P][ldx].  PLANES = true: the same rows written directly as interleaved 16-bit planes
-// (fp16 planes p16 = first-layer operand, optional bf16 planes pb = weight-gradient operand), so the MLP never
-// sees an fp32 copy of the 576-wide encoding (saves the 151 MB write and the hos_split_planes2 pass per level).
-template <bool PLANES>
-__global__ __launch_bounds__(256) void encode_ipe_kernel(
-    const float* __restrict__ tdist, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-    const float* __restrict__ radii, const float* __restrict__ basis, const float* __restrict__ embed,
-    int B, int S, float* __restrict__ X, int ldx, unsigned short* __restrict__ p16, unsigned short* __restrict__ pb) {
-    __shared__ float s_mean[SB][3];
-    __shared__ float s_cov[SB][9];
-    __shared__ float s_lm[SB][NDIR];
-    __shared__ float s_lv[SB][NDIR];
-    __shared__ float s_basis[3][NDIR];
-    __shared__ float s_embed[NEMB];
-    __shared__ int s_big;              // some |2^11 * lifted mean| of this block is beyond enc_sin's range: library sinf for the block
+// H:37-42: the contraction z of x and its closed-form Jacobian J (the identity on r2 <= 1; r2 is clamped at 1e-32, so x = 0 takes that branch)
+__device__ __forceinline__ void contract_point(const float (&x)[3], float (&z)[3], float (&J)[3][3]) {
+    const float r2 = fmaxf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2], 1e-32f);
+    if (r2 <= 1.f) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            z[a] = x[a];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) J[a][c] = (a == c) ? 1.f : 0.f;
+        }
+    } else {
+        const float r = sqrtf(r2);
+        const float sc = (2.f * r - 1.f) / r2;
+        const float cc = (2.f / (r2 * r) - 2.f / r2) / r;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            z[a] = sc * x[a];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) J[a][c] = (a == c ? sc : 0.f) + cc * (x[a] * x[c]);
+        }
+    }
+}
 
-    const int t = threadIdx.x;
-    const long P = (long)B * S;
-    const long p0 = (long)blockIdx.x * SB;
-    if (t < 3 * NDIR) s_basis[t / NDIR][t % NDIR] = basis[t];
-    if (t == 255) s_big = 0;
-    if (t >= 64 && t < 64 + NEMB) s_embed[t - 64] = embed[t - 64];
-
-    if (t < SB && p0 + t < P) {
-        const long p = p0 + t;
+// First stage of the encoder: sample p -> contracted mean z [3] and covariance J cov J^T [9], the one part the two encoders do not share.
+// FrustumStage: the conical frustum of sample p % S of ray p / S (hos_encode_ipe / _planes; its operations and their order are
+// the kernel's of before the split, so these entries' outputs are unchanged bit for bit).
+struct FrustumStage {
+    const float* __restrict__ tdist; const float* __restrict__ rays_o; const float* __restrict__ rays_d; const float* __restrict__ radii;
+    int S;
+    __device__ __forceinline__ void operator()(long p, float* __restrict__ mean, float* __restrict__ covo) const {
         const int ray = (int)(p / S), s = (int)(p % S);
         const float t0 = tdist[(size_t)ray * (S + 1) + s], t1 = tdist[(size_t)ray * (S + 1) + s + 1];
         const float ox = rays_o[ray * 3 + 0], oy = rays_o[ray * 3 + 1], oz = rays_o[ray * 3 + 2];
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
         r_var *= rad * rad;
         // H:320-338 (diag=False)
         const float dmag = fmaxf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], 1e-10f);
-        float x[3] = {d[0] * t_mean + ox, d[1] * t_mean + oy, d[2] * t_mean + oz};
+        const float x[3] = {d[0] * t_mean + ox, d[1] * t_mean + oy, d[2] * t_mean + oz};
         float cov[3][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
@@ -125,28 +133,9 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
                 const float nul = (a == c ? 1.f : 0.f) - d[a] * (d[c] / dmag);
                 cov[a][c] = t_var * outer + r_var * nul;
             }
-        // H:37-42 contraction and its Jacobian
-        const float r2 = fmaxf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2], 1e-32f);
         float J[3][3];
         float z[3];
-        if (r2 <= 1.f) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                z[a] = x[a];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) J[a][c] = (a == c) ? 1.f : 0.f;
-            }
-        } else {
-            const float r = sqrtf(r2);
-            const float sc = (2.f * r - 1.f) / r2;
-            const float cc = (2.f / (r2 * r) - 2.f / r2) / r;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                z[a] = sc * x[a];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) J[a][c] = (a == c ? sc : 0.f) + cc * (x[a] * x[c]);
-            }
-        }
+        contract_point(x, z, J);
         float JC[3][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
@@ -154,10 +143,64 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
             for (int c = 0; c < 3; ++c) JC[a][c] = J[a][0] * cov[0][c] + J[a][1] * cov[1][c] + J[a][2] * cov[2][c];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            s_mean[t][a] = z[a];
+            mean[a] = z[a];
 #pragma unroll
             for (int c = 0; c < 3; ++c)   // (J cov) J^T
-                s_cov[t][a * 3 + c] = JC[a][0] * J[c][0] + JC[a][1] * J[c][1] + JC[a][2] * J[c][2];
+                covo[a * 3 + c] = JC[a][0] * J[c][0] + JC[a][1] * J[c][1] + JC[a][2] * J[c][2];
+        }
+    }
+};
+// PointStage: the isotropic Gaussian (pts[p], var I) (hos_encode_ipe_points / _planes): J (var I) J^T written as var (J J^T) -- no
+// covariance to build and one 3x3 product instead of two.  Inside the unit ball J = I: the covariance is var I exactly; var = 0 gives
+// an all-zero covariance, a lifted variance of 0 and a damping enc_exp(-0) = 1 exactly.
+struct PointStage {
+    const float* __restrict__ pts; float var;
+    __device__ __forceinline__ void operator()(long p, float* __restrict__ mean, float* __restrict__ covo) const {
+        const float x[3] = {pts[(size_t)p * 3 + 0], pts[(size_t)p * 3 + 1], pts[(size_t)p * 3 + 2]};
+        float J[3][3];
+        float z[3];
+        contract_point(x, z, J);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            mean[a] = z[a];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) covo[a * 3 + c] = var * (J[a][0] * J[c][0] + J[a][1] * J[c][1] + J[a][2] * J[c][2]);
+        }
+    }
+};
+
+// One kernel for both encoders: `first` (FrustumStage / PointStage) fills the block's means and covariances, everything after the
+// first barrier -- lift, feature loop with the block-uniform sine choice, tail -- is shared.  P rows, indexed in 64 bits.
+// PLANES = false: X fp32 [P][ldx].  PLANES = true: the same rows written directly as interleaved 16-bit planes
+// (fp16 planes p16 = first-layer operand, optional bf16 planes pb = weight-gradient operand), so the MLP never
+// sees an fp32 copy of the 576-wide encoding (saves the 151 MB write and the hos_split_planes2 pass per level).
+template <bool PLANES, typename Stage>
+__global__ __launch_bounds__(256) void encode_ipe_kernel(
+    const Stage first, const float* __restrict__ basis, const float* __restrict__ embed,
+    const long P, float* __restrict__ X, int ldx, unsigned short* __restrict__ p16, unsigned short* __restrict__ pb) {
+    __shared__ float s_mean[SB][3];
+    __shared__ float s_cov[SB][9];
+    __shared__ float s_lm[SB][NDIR];
+    __shared__ float s_lv[SB][NDIR];
+    __shared__ float s_basis[3][NDIR];
+    __shared__ float s_embed[NEMB];
+    __shared__ int s_big;              // some |2^11 * lifted mean| of this block is beyond enc_sin's range: library sinf for the block
+
+    const int t = threadIdx.x;
+    const long p0 = (long)blockIdx.x * SB;
+    if (t < 3 * NDIR) s_basis[t / NDIR][t % NDIR] = basis[t];
+    if (t == 255) s_big = 0;
+    if (t >= 64 && t < 64 + NEMB) s_embed[t - 64] = embed[t - 64];
+
+    if (t < SB) {
+        if (p0 + t < P) {
+            first(p0 + t, s_mean[t], s_cov[t]);
+        } else {
+            // rows past P of the last block: zeros, so that what the lift reads there never decides `s_big` for the block's real rows
+#pragma unroll
+            for (int a = 0; a < 3; ++a) s_mean[t][a] = 0.f;
+#pragma unroll
+            for (int a = 0; a < 9; ++a) s_cov[t][a] = 0.f;
         }
     }
     __syncthreads();
@@ -205,6 +248,10 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
         // bound by VALU issue.  Round 5, same box, per 262 144 / 131 072 / 4 194 304 samples, one plane format
         // (profiles/r05_encoder_variants.txt): per-item loop + library sinf / expf 226 / 114 / 3025 us; this loop + library 189 / 89 /
         // 2533; + enc_sin 181 / 81 / 2379; + enc_exp 169 / 76 / 2284 (kept); hardware v_sin / v_exp (NOT to parity) 149 / 58 / 2214.
+        // The point encoder (PointStage; scripts/bkgd_mesh_cost.py, profiles/bkgd_mesh_cost.json, another box and day than the 169 us
+        // above): 156 us per 262 144 rows (min 149), the frustum encoder 158 us (min 151) alternating with it in the same process, bf16
+        // planes only.  The first stage is 64 of 256 threads once per block, so dropping the covariance build and one 3x3 product is
+        // within the run-to-run spread: this loop's 756 sine / exponential evaluations per row are the time of either kernel.
         if (t < 2 * (HALF / 2)) {
             const int q = t % (HALF / 2), sub = t / (HALF / 2);
             const int c = 2 * q;
@@ -280,8 +327,8 @@ extern "C" int hos_encode_ipe(const float* tdist, const float* rays_o, const flo
     if (!tdist || !rays_o || !rays_d || !radii || !basis || !embed || !X || B <= 0 || S <= 0) return HOS_E_ARG;
     if (ldx < NIPE + NEMB) return HOS_E_SHAPE;
     const long P = (long)B * S;
-    hipLaunchKernelGGL(encode_ipe_kernel<false>, dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), tdist, rays_o, rays_d, radii, basis, embed, B, S, X, ldx,
+    hipLaunchKernelGGL((encode_ipe_kernel<false, FrustumStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), FrustumStage{tdist, rays_o, rays_d, radii, S}, basis, embed, P, X, ldx,
                        (unsigned short*)nullptr, (unsigned short*)nullptr);
     return hos_launch_status();
 }
@@ -292,8 +339,29 @@ extern "C" int hos_encode_ipe_planes(const float* tdist, const float* rays_o, co
     if (!tdist || !rays_o || !rays_d || !radii || !basis || !embed || (!p16 && !pb) || B <= 0 || S <= 0) return HOS_E_ARG;
     if (ld < NIPE + NEMB || (ld & 31)) return HOS_E_SHAPE;
     const long P = (long)B * S;
-    hipLaunchKernelGGL(encode_ipe_kernel<true>, dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), tdist, rays_o, rays_d, radii, basis, embed, B, S, (float*)nullptr, ld,
+    hipLaunchKernelGGL((encode_ipe_kernel<true, FrustumStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), FrustumStage{tdist, rays_o, rays_d, radii, S}, basis, embed, P, (float*)nullptr, ld,
+                       (unsigned short*)p16, (unsigned short*)pb);
+    return hos_launch_status();
+}
+
+// The grid of 64-row workgroups is one 32-bit dimension: P <= 64 * (2^31 - 1) rows (a 5000^3 grid), HOS_E_SHAPE beyond.
+extern "C" int hos_encode_ipe_points(const float* pts, int64_t P, float var, const float* basis, const float* embed, float* X, int ldx,
+                                     hos_stream_t stream) {
+    if (!pts || !basis || !embed || !X || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
+    if (ldx < NIPE + NEMB || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
+    hipLaunchKernelGGL((encode_ipe_kernel<false, PointStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), PointStage{pts, var}, basis, embed, (long)P, X, ldx,
+                       (unsigned short*)nullptr, (unsigned short*)nullptr);
+    return hos_launch_status();
+}
+
+extern "C" int hos_encode_ipe_points_planes(const float* pts, int64_t P, float var, const float* basis, const float* embed, void* p16,
+                                            void* pb, int ld, hos_stream_t stream) {
+    if (!pts || !basis || !embed || (!p16 && !pb) || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
+    if (ld < NIPE + NEMB || (ld & 31) || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
+    hipLaunchKernelGGL((encode_ipe_kernel<true, PointStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), PointStage{pts, var}, basis, embed, (long)P, (float*)nullptr, ld,
                        (unsigned short*)p16, (unsigned short*)pb);
     return hos_launch_status();
 }

@@ -7,6 +7,7 @@
 //   hos_grid_warp          the frame mesh: the backward LBS (N:304-355) of a range of grid vertices of the frame's own box -> x_skel, mask,
 //                          the rows the non-rigid chain and the canonical MLP are evaluated on (the renderer's warp, on a grid)
 //   hos_grid_alpha_masked  hos_grid_alpha with that mask given (one kernel template, two instantiations)
+//   hos_grid_alpha_density the background mesh (mesh.bkgd_field): alpha = 1 - exp(-density h), no mask, from the NeRF MLP's densities
 //   hos_mesh_vertex_normals  per mesh vertex the normalised negative central difference of the trilinear field, spacing h
 //   hos_march_tets_count   marching tetrahedra, count / scan: per 256-vertex block the mesh vertices its grid vertices own and the
 //   hos_march_tets_write   triangles of its cells; one scan workgroup; the write pass at block offsets (as hos_raybank.hip)
@@ -134,6 +135,17 @@ __global__ __launch_bounds__(MT_BLOCK) void grid_alpha_kernel(const float* __res
 #pragma unroll
         for (int c = 0; c < 3; ++c) rgb[u * 3 + c] = raw[r * 4 + c];
     }
+}
+
+// The background mesh: no mask and no colour on the grid -- alpha = 1 - exp(-density h) of a range of vertices, 0 on the rim.
+__global__ __launch_bounds__(MT_BLOCK) void grid_alpha_density_kernel(const float* __restrict__ density, MeshGrid g, long first, long count,
+                                                                      float* __restrict__ alpha) {
+    const long r = (long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (r >= count) return;
+    const long u = first + r;
+    const int ix = (int)(u % g.Nx), iy = (int)((u / g.Nx) % g.Ny), iz = (int)(u / ((long)g.Nx * g.Ny));
+    const bool rim = ix == 0 || iy == 0 || iz == 0 || ix == g.Nx - 1 || iy == g.Ny - 1 || iz == g.Nz - 1;
+    alpha[u] = rim ? 0.f : 1.f - expf(-density[r] * g.h);
 }
 
 // ------------------------------------------------------------------------------------------ marching tetrahedra
@@ -451,6 +463,19 @@ extern "C" int hos_grid_alpha_masked(const float* raw, const float* mask, float 
     hipLaunchKernelGGL(grid_alpha_kernel<true>, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
                        static_cast<hipStream_t>(stream), raw, mask, 0, 0, (const float*)nullptr, (const float*)nullptr, g, (long)first,
                        (long)count, alpha, rgb);
+    return hos_launch_status();
+}
+
+extern "C" int hos_grid_alpha_density(const float* density, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* alpha,
+                                      hos_stream_t stream) {
+    if (!density || !alpha) return HOS_E_ARG;
+    long N;
+    if (int e = mesh_shape(Nx, Ny, Nz, &N)) return e;
+    if (first < 0 || count < 0 || first > N || count > N - first) return HOS_E_ARG;
+    if (count == 0) return HOS_OK;
+    const MeshGrid g{Nx, Ny, Nz, 0.f, 0.f, 0.f, h};
+    hipLaunchKernelGGL(grid_alpha_density_kernel, dim3((unsigned)((count + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0,
+                       static_cast<hipStream_t>(stream), density, g, (long)first, (long)count, alpha);
     return hos_launch_status();
 }
 

@@ -40,9 +40,27 @@ parameters, as unmeasured on a real scene as they are for the canonical mesh.  E
 correspondence between frames.
 
 Normals (`normals=True`, both meshes): per vertex the normalised negative central difference, step h, of the field's trilinear
-interpolant (`ops.mesh_vertex_normals`), so they follow the field the surface was cut from and need no face adjacency."""
+interpolant (`ops.mesh_vertex_normals`), so they follow the field the surface was cut from and need no face adjacency.
+
+The background mesh (`bkgd_field`, `extract_bkgd`): the scene those meshes stand in -- the state-conditional mip-NeRF-360 model of
+stage 1, which is also stage 3's background branch -- per object state, in the background rays' own space: the scaled world that
+`extract_frame(space="world")` writes, so the two load aligned.  For a point x of `grid_of_box(box)` (spacing h) and the state s of
+`time`:
+
+    sigma_s(x) = density of the NeRF MLP (`model.mlps[-1]`, not a proposal MLP) at the Gaussian (x, h^2/12 I)
+    alpha(x)   = 0 on the outermost vertex layer, else 1 - exp(-sigma_s(x) * h)
+
+h^2/12 is the per-axis variance of a uniform voxel of side h: the voxel plays the role the conical frustum plays for a ray sample
+(`MipNeRF360MLP.query_points`, hos_encode_ipe_points: contraction, var J J^T, integrated positional encoding).  alpha is the alpha of
+`compute_alpha_weights` (H:235-261) for a sample as long as a voxel: the definition of the human-object meshes without a mask.  The
+box may reach beyond the unit ball, the contraction takes any point; the default launcher box is the cube [-1,1]^3 about the region
+the contraction leaves linear.  The zero rim closes the surface, so WHERE THE BOX CUTS SOLID MATTER (the ground, a wall) THE MESH IS
+CAPPED by faces on the box's walls: they are the box, not the scene.  The NeRF MLP's colour depends on the view direction: the
+vertex colours come from a second query at the mesh vertices, each seen head-on (view direction = -normal; (0,0,-1) where the normal
+is the zero vector).  Level 0.5 and resolution 256 are the same parameters, as unmeasured on a real scene as for the other two meshes."""
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict
 
@@ -247,3 +265,107 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
             "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
             "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"], "normals": vn, "space": space, "to_world": to_world,
             "frame_name": pose.get("frame_name"), "time": None if time is None else float(time)}
+
+
+# ------------------------------------------------------------------------------------------ the background mesh
+HEAD_ON_FALLBACK = (0.0, 0.0, -1.0)          # the view direction of a vertex whose normal is the zero vector
+
+
+@contextlib.contextmanager
+def _evaluating_bkgd(model):
+    """`evaluating` for a `MipNeRF360` (it has no `cfg.perturb` to silence): eval mode, no autograd."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield model
+    finally:
+        model.train(was_training)
+
+
+def _box_corners(box):
+    b = np.asarray(box, dtype=np.float64).reshape(-1)
+    if b.shape != (6,):
+        raise ValueError(f"box must be (xmin, ymin, zmin, xmax, ymax, zmax), got {box!r}")
+    return b[:3], b[3:]
+
+
+def voxel_variance(spacing) -> float:
+    """h^2 / 12 in fp32: the per-axis variance of a uniform voxel of side h, the `var` of every background-mesh query."""
+    h = np.float32(spacing)
+    return float(np.float32(h * h) / np.float32(12.0))
+
+
+def bkgd_field(model, box, time: float, resolution: int = 256, chunk: int = 1 << 18) -> Dict:
+    """alpha [Nz,Ny,Nx] of the background `model` (a `MipNeRF360`: stage 1's, or `HOSNeRF.model`) on `grid_of_box` of `box` =
+    (xmin, ymin, zmin, xmax, ymax, zmax), for the object state of `time` (module docstring).  Under eval mode, `no_grad` and
+    `ops.guarded_forward`; per chunk of `chunk` vertices (the last one shorter) `ops.grid_points`, the NeRF MLP's `query_points` with
+    var = h^2/12 and `ops.grid_alpha_density`.  The view head runs on a constant direction and its colours are dropped (a few
+    percent of the trunk's work).  Also returns `density` [Nz,Ny,Nx], what alpha was computed from."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"bkgd_field: chunk {chunk} < 1")
+    bmin, bmax = _box_corners(box)
+    grid = grid_of_box(bmin, bmax, resolution)
+    origin, h, dims = grid["origin"], grid["spacing"], grid["dims"]
+    Nx, Ny, Nz = dims
+    N = Nx * Ny * Nz
+    mlp = model.mlps[-1]
+    dev = model.flat_param.device
+    state = select_state(float(time), mlp.transitions_times)
+    var = voxel_variance(h)
+    alpha = torch.empty(Nz, Ny, Nx, device=dev)
+    density = torch.empty(Nz, Ny, Nx, device=dev)
+    flat = density.view(-1)
+    view = torch.tensor([HEAD_ON_FALLBACK], device=dev)
+
+    def run():
+        for first in range(0, N, chunk):
+            rows = min(chunk, N - first)
+            pts = ops.grid_points(origin, h, dims, first, rows, device=dev)
+            d = mlp.query_points(pts, var, view.expand(rows, 3).contiguous(), float(time))["density"]
+            flat[first:first + rows] = d
+            ops.grid_alpha_density(d, h, dims, first, alpha)
+
+    with _evaluating_bkgd(model):
+        ops.guarded_forward(model, dev, run)
+    return {"alpha": alpha, "density": density, "origin": origin, "spacing": h, "dims": dims, "state": state, "var": var,
+            "box": [float(x) for x in bmin] + [float(x) for x in bmax]}
+
+
+def head_on_viewdirs(normals: torch.Tensor) -> torch.Tensor:
+    """-normal per vertex, `HEAD_ON_FALLBACK` where the normal is the exact zero vector."""
+    zero = (normals == 0).all(dim=1, keepdim=True)
+    return torch.where(zero, torch.tensor(HEAD_ON_FALLBACK, device=normals.device).expand_as(normals), -normals).contiguous()
+
+
+def extract_bkgd(model, box, time: float, resolution: int = 256, level: float = 0.5, normals: bool = True, chunk: int = 1 << 18) -> Dict:
+    """The mesh of the background at `time`'s object state inside `box`: `bkgd_field`, `ops.march_tets` at `level`,
+    `ops.mesh_vertex_normals`, then the colours from a second `query_points` at the vertices (same var, view direction
+    `head_on_viewdirs`).  Returns what `extract` returns -- `vertices` f32 [V,3] in the background rays' space (the scaled world),
+    `faces` int32 [F,3], `colors` uint8 [V,3] (the truncation of `to_8b_image`), `normals` f32 [V,3] (None with `normals=False`: they
+    are computed regardless, the colours need them), `origin`, `spacing`, `dims`, `state`, `volume`, `area`, `level`, `alpha` -- plus
+    `vertex_rgb` f32 [V,3] (the colours before truncation), `density`, `var` and `box`.  `level` and `resolution` are unmeasured
+    defaults; the surface is capped where the box cuts solid matter (module docstring)."""
+    field = bkgd_field(model, box, time, resolution, chunk)
+    vertices, _, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"])
+    vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices)
+    V = vertices.shape[0]
+    dev = vertices.device
+    rgb = torch.empty(V, 3, device=dev)
+    mlp = model.mlps[-1]
+    view = head_on_viewdirs(vn)
+
+    def run():
+        for first in range(0, V, int(chunk)):
+            sl = slice(first, min(first + int(chunk), V))
+            rgb[sl] = mlp.query_points(vertices[sl].contiguous(), field["var"], view[sl].contiguous(), float(time))["rgb"]
+
+    if V > 0:
+        with _evaluating_bkgd(model):
+            ops.guarded_forward(model, dev, run)
+    volume, area = mesh_measures(vertices, faces)
+    return {"vertices": vertices, "faces": faces, "colors": (255.0 * rgb.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
+            "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
+            "level": float(level), "alpha": field["alpha"], "normals": vn if normals else None, "vertex_rgb": rgb,
+            "density": field["density"], "var": field["var"], "box": field["box"]}

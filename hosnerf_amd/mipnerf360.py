@@ -522,6 +522,27 @@ class MipNeRF360MLP(FlatModule):
         rgb = self._zero_rgb(B, S, density.device) if self.disable_rgb else rgb.view(B, S, 3)
         return {"density": density, "rgb": rgb}
 
+    def query_points(self, pts, var: float, viewdirs, time: float) -> Dict[str, torch.Tensor]:
+        """The MLP at P isotropic Gaussians given directly -- mean `pts[p]` ([P,3]), covariance `var * I` -- for the object state of
+        `time`: what the reference's `forward(means, covs)` takes, where `query` builds its Gaussians from rays inside the encoder.
+        `viewdirs` [P,3], one per point.  -> {"density" [P], "rgb" [P,3]}.  Everything behind the encoding is `query`'s no-grad path
+        (the same planes / fp32 choice); evaluation only: an error under autograd (the mesh extraction has nothing to train)."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("MipNeRF360MLP.query_points is an evaluation output: call it under torch.no_grad()")
+        P = pts.shape[0]
+        if viewdirs.shape != pts.shape:
+            raise ValueError(f"query_points: viewdirs {tuple(viewdirs.shape)} must be one direction per point, {tuple(pts.shape)}")
+        state = select_state(time, self.transitions_times)
+        embed = self._embeds.view(self.store.param)[state]
+        pts = pts.contiguous()
+        if self._use_planes():
+            one_fmt = self._bf16_fwd()
+            X = ops.encode_ipe_points_planes(pts, var, self.pos_basis_t, embed, X_LD, want_bf16=one_fmt, want_fp16=not one_fmt)
+        else:
+            X = ops.encode_ipe_points(pts, var, self.pos_basis_t, embed, X_LD)
+        density, rgb, _ = self._forward_impl(X, viewdirs.contiguous(), P, 1, save=False)
+        return {"density": density, "rgb": self._zero_rgb(P, 1, density.device).view(P, 3) if self.disable_rgb else rgb}
+
 
 class _MLPFn(torch.autograd.Function):
     """Autograd node for one MLP query.  Parameter gradients are accumulated straight into the flat

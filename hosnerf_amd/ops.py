@@ -969,6 +969,34 @@ def encode_ipe_planes(tdist, rays_o, rays_d, radii, basis, embed, ldx: int = 576
     return p16, pb
 
 
+def _points_args(pts, var):
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+        raise _lib.HosLibraryError(f"encode_ipe_points: pts must be [P,3] with P > 0, got {tuple(pts.shape)}")
+    var = float(var)
+    if not var >= 0.0:
+        raise _lib.HosLibraryError(f"encode_ipe_points: var = {var} (the variance of the isotropic Gaussian: >= 0)")
+    return int(pts.shape[0]), var
+
+
+def encode_ipe_points(pts, var: float, basis, embed, ldx: int = 576, out=None):
+    """X [P, ldx] of `encode_ipe` for P Gaussians given directly: mean `pts[p]` ([P,3]), covariance `var * I` (var >= 0; 0 = no
+    damping) -- contraction, Sigma' = var J J^T, lift, IPE, [IPE | embed | 0] (hos_encode.hip: the frustum encoder after its first
+    stage).  No gradient flows through it."""
+    P, var = _points_args(pts, var)
+    X = torch.empty(P, ldx, device=pts.device) if out is None else out
+    call("hos_encode_ipe_points", ptr(pts), P, var, ptr(basis), ptr(embed), ptr(X), ldx)
+    return X
+
+
+def encode_ipe_points_planes(pts, var: float, basis, embed, ldx: int = 576, want_bf16: bool = True, want_fp16: bool = True):
+    """`encode_ipe_points`, the rows written directly as Planes (fp16 if want_fp16, bf16 if want_bf16), as `encode_ipe_planes`."""
+    P, var = _points_args(pts, var)
+    p16 = Planes.empty(P, ldx, torch.float16, pts.device) if want_fp16 else None
+    pb = Planes.empty(P, ldx, torch.bfloat16, pts.device) if want_bf16 else None
+    call("hos_encode_ipe_points_planes", ptr(pts), P, var, ptr(basis), ptr(embed), _pp(p16), _pp(pb), ldx)
+    return p16, pb
+
+
 def encode_viewdirs(viewdirs, S: int, Xv: torch.Tensor, col0: int):
     B = viewdirs.shape[0]
     call("hos_encode_viewdirs", ptr(viewdirs), B, S, ptr(Xv), Xv.stride(0), col0)
@@ -2053,6 +2081,19 @@ def grid_alpha_masked(raw, mask, origin, spacing, dims, first: int, alpha, rgb=N
         raise _lib.HosLibraryError(f"grid_alpha_masked: alpha {tuple(alpha.shape)} / rgb / raw {tuple(raw.shape)} / mask {tuple(mask.shape)} do not fit a grid of {tuple(dims)}")
     if count > 0:
         call("hos_grid_alpha_masked", ptr(raw), ptr(mask), *_grid_args(origin, spacing, dims), int(first), count, ptr(alpha), ptr(rgb))
+    return alpha
+
+
+def grid_alpha_density(density, spacing, dims, first: int, alpha):
+    """The background mesh's field: alpha[first + r] = 1 - exp(-density[r] * spacing) for the vertices `density` [count] was evaluated
+    at, 0 on the grid's outermost layer; `alpha` [Nz,Ny,Nx] is the whole-grid tensor, written in place.  One launch."""
+    density = density.reshape(-1)
+    count = density.shape[0]
+    Nx, Ny, Nz = (int(d) for d in dims)
+    if alpha.numel() != Nx * Ny * Nz:
+        raise _lib.HosLibraryError(f"grid_alpha_density: alpha {tuple(alpha.shape)} does not fit a grid of {tuple(dims)}")
+    if count > 0:
+        call("hos_grid_alpha_density", ptr(density), float(np.float32(spacing)), Nx, Ny, Nz, int(first), count, ptr(alpha))
     return alpha
 
 

@@ -390,6 +390,16 @@ int hos_encode_ipe_planes(const float* tdist, const float* rays_o, const float* 
                           const float* basis, const float* embed, int B, int S, void* p16, void* pb, int ld,
                           hos_stream_t stream);
 
+/* The same encoding of P isotropic Gaussians given directly: row p = the Gaussian with mean pts[p] (pts [P,3]) and covariance var * I
+ * (var >= 0; 0 is legal: no damping).  Contraction with its closed-form Jacobian J, Sigma' = var * (J J^T) (= var * I where |x|^2 <= 1,
+ * the origin included), then the lift, the IPE and the [IPE(504) | embed(64) | 0-pad] row of hos_encode_ipe -- the same kernel after
+ * its first stage, the same two layouts.  Rows are indexed in 64 bits.  HOS_E_ARG: a null pointer, P <= 0, var < 0 or NaN;
+ * HOS_E_SHAPE: ldx < 568 (planes: ld < 568 or ld % 32 != 0) or P > 64 * (2^31 - 1). */
+int hos_encode_ipe_points(const float* pts, int64_t P, float var, const float* basis, const float* embed, float* X, int ldx,
+                          hos_stream_t stream);
+int hos_encode_ipe_points_planes(const float* pts, int64_t P, float var, const float* basis, const float* embed, void* p16, void* pb,
+                                 int ld, hos_stream_t stream);
+
 /* View-direction encoding (H:93-100, deg 0..4, identity appended = 27) broadcast over samples
  * into columns [col0, col0+27) of Xv [B*S, ldx]; columns [col0+27, ldx) are zeroed (M:330-335). */
 int hos_encode_viewdirs(const float* viewdirs, int B, int S, float* Xv, int ldx, int col0,
@@ -906,6 +916,13 @@ int hos_grid_warp(const float* R_b, const float* T_b, const float* vol, int V, i
  * rgb[first + r, :] = raw[r, :3] when rgb != NULL.  raw [count,4], mask [count] (what hos_grid_warp wrote for the range). */
 int hos_grid_alpha_masked(const float* raw, const float* mask, float ox, float oy, float oz, float h, int Nx, int Ny, int Nz, int64_t first,
                           int64_t count, float* alpha, float* rgb, hos_stream_t stream);
+
+/* The background mesh: alpha[first + r] = 1 - exp(-density[r] * h) for the vertices [first, first + count) of the grid, exactly 0 on the
+ * outermost vertex layer (the rule that closes every surface); density [count] = the NeRF MLP's at hos_grid_points' positions, alpha
+ * [Nx*Ny*Nz] the WHOLE-grid array.  No mask and no colour (the background's colour depends on the view: it is queried at the mesh
+ * vertices).  A range outside the grid HOS_E_ARG; count = 0 launches nothing. */
+int hos_grid_alpha_density(const float* density, float h, int Nx, int Ny, int Nz, int64_t first, int64_t count, float* alpha,
+                           hos_stream_t stream);
 
 /* normals [V,3] of mesh vertices [V,3] from the whole-grid field [Nz,Ny,Nx] they were extracted from:
  *   g_a = T(v + h e_a) - T(v - h e_a), a = x, y, z;   n = -g / |g|, and (0,0,0) where g is 0 or not finite.  |g| is taken of

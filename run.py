@@ -19,6 +19,9 @@ a triangle mesh, <logdir>/mesh/time_<t>.ply + meshes.json (`hosnerf_amd/mesh.py`
 `run.run_mesh_frames` (same stages, same two parameters; this build's addition) writes the POSED human-object of each frame that
 `run.run_eval` would choose (`--eval_skip`), through the renderer's backward warp and in the scene's coordinates,
 <logdir>/mesh_frames/<frame_name>.ply + meshes.json (`mesh.extract_frame`; `run.mesh_space` "world" | "body", `run.mesh_normals` True).
+`run.run_mesh_bkgd` (stages 1 and 3, with `--scene_dir`; this build's addition) writes the BACKGROUND scene of every object state as
+a triangle mesh in the same scaled-world coordinates, <logdir>/mesh_bkgd/time_<t>.ply + meshes.json (`mesh.extract_bkgd`;
+`run.mesh_bkgd_box` (-1,-1,-1, 1,1,1), the same `run.mesh_resolution` / `run.mesh_level`).
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -144,6 +147,10 @@ def run(args, gin):
         raise SystemExit("run.run_mesh_frames extracts the posed human-object of each frame (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
     if bool(kw.get("run_mesh_frames", False)) and str(kw.get("mesh_space", "world")) not in ("world", "body"):
         raise SystemExit(f"run.mesh_space = {kw.get('mesh_space')!r}: \"world\" (the scene's coordinates) or \"body\" (the frame's body frame)")
+    if bool(kw.get("run_mesh_bkgd", False)):
+        if model_name == "state_humanobject":
+            raise SystemExit("run.run_mesh_bkgd extracts the background scene (stage 1 `state_mipnerf360`, stage 3 `hosnerf`); stage 2 has no background model")
+        mesh_bkgd_box(kw)                             # an empty or non-finite box stops the run before anything is trained
     dataset_name = kw.get("dataset_name", "synthetic")
     scene = args.scene_name or "scene"
     exp_name = f"{model_name}_{dataset_name}_{scene}_{str(args.seed).zfill(3)}"          # S3/run.py:108-110
@@ -333,6 +340,8 @@ def run(args, gin):
         result["mesh"] = extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world)
     if bool(kw.get("run_mesh_frames", False)):
         result["mesh_frames"] = extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world)
+    if bool(kw.get("run_mesh_bkgd", False)):
+        result["mesh_bkgd"] = extract_bkgd_meshes(kw, lit, model_name, scene if bank is None else bank, ckpt, logdir, dev, rank, world)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -612,6 +621,46 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     if rank == 0:
         print(f"[run] frame meshes: {len(idxs)} frames at resolution {resolution}, level {level}, space {space} written to {os.path.join(logdir, 'mesh_frames')}")
     return {"frames": [r["frame_name"] for r in rows], "resolution": resolution, "level": level, "space": space}
+
+
+def mesh_bkgd_box(kw):
+    """`run.mesh_bkgd_box` = (xmin, ymin, zmin, xmax, ymax, zmax), default the cube (-1,-1,-1, 1,1,1) about the region the scene
+    contraction leaves linear; a larger box is legal (the contraction takes any point).  Six finite numbers with min < max on every
+    axis, or the run stops."""
+    box = kw.get("mesh_bkgd_box", (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0))
+    try:
+        b = [float(x) for x in box]
+    except (TypeError, ValueError):
+        b = []
+    if len(b) != 6 or not all(x == x and abs(x) != float("inf") for x in b) or not all(b[a] < b[a + 3] for a in range(3)):
+        raise SystemExit(f"run.mesh_bkgd_box = {box!r}: (xmin, ymin, zmin, xmax, ymax, zmax), finite, with min < max on every axis")
+    return b
+
+
+def extract_bkgd_meshes(kw, lit, model_name, source, ckpt, logdir, dev, rank, world):
+    """`run.run_mesh_bkgd` (this build's addition; stage 1 and stage 3): the background scene of every object state as a triangle
+    mesh, from `last.ckpt`, at the times of `tpose.tpose_times` -- `mesh.extract_bkgd` inside `run.mesh_bkgd_box` at
+    `run.mesh_resolution` (256) and `run.mesh_level` (0.5) -> <logdir>/mesh_bkgd/time_{:06}.ply (binary PLY: position, nx ny nz,
+    colour seen head-on) and <logdir>/mesh_bkgd/meshes.json (per time: the fields of mesh/meshes.json plus box).  The vertices are
+    in the background rays' own space, the scene's scaled world: the space the stage-3 z-merge maps the human samples into by
+    `newsmpl_to_scale_world` (hosnerf.py, `ops.merge_composite`) and therefore the one `run.mesh_space = "world"` writes the frame
+    meshes in -- mesh_frames/*.ply and mesh_bkgd/*.ply load aligned.  With several ranks the states are dealt round-robin, each rank
+    writes its own .ply and rank 0 the JSON.  `results.json` is not touched."""
+    from hosnerf_amd import mesh, tpose
+    load_last(lit, source, ckpt, "run.run_mesh_bkgd", "the scene whose checkpoint is meshed")
+    resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
+    box = mesh_bkgd_box(kw)
+    model = lit.model if model_name == "state_mipnerf360" else lit.net.model
+    times = tpose.tpose_times(model.mlps[-1].transitions_times)
+
+    def job(j):
+        m = mesh.extract_bkgd(model, box, times[j], resolution=resolution, level=level)
+        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level), "box": m["box"]}
+
+    write_mesh_set(os.path.join(logdir, "mesh_bkgd"), len(times), rank, world, job, lambda r: "time_{:06}".format(r["time"]))
+    if rank == 0:
+        print(f"[run] background mesh: {len(times)} object states at resolution {resolution}, level {level}, box {box} written to {os.path.join(logdir, 'mesh_bkgd')}")
+    return {"times": times, "resolution": resolution, "level": level, "box": box}
 
 
 def main(argv=None):
