@@ -188,6 +188,33 @@ class SceneItems:
         item.update(frame_name=name, time=float(self.times[idx]), is_train=False, iter_val=torch.full((1,), 1e7))
         return item
 
+    def frame_camera(self, idx: int) -> Dict:
+        """The frame's own camera without any rays (stage 2 and 3), as `_camera` and `eval_frame` compute it: `K` [3,3] (scaled by
+        `resize_img_scale`) and `E` [4,4] (the body-frame camera after `smpl_frame_camera`: X_cam = E[:3,:3] p + E[:3,3] for a point p
+        of the frame's body space, the space of the item's `rays` and of `mesh.extract_frame(space="body")`) as host float64 arrays,
+        `E_colmap` (the background-world camera `scaleworld_to_camera`; None where the scene's cameras hold none) and the frame's
+        `H`, `W`.  What `mesh.rasterize` takes."""
+        name = self.frames[idx]
+        K, E, _ = self._camera(name)
+        Ec = self.cameras[name].get("scaleworld_to_camera")
+        H, W = int(self.images.shape[1]), int(self.images.shape[2])
+        return {"K": K, "E": np.asarray(E, dtype=np.float64), "E_colmap": None if Ec is None else np.asarray(Ec, dtype=np.float64), "H": H, "W": W}
+
+    def human_frame(self, idx: int, bgcolor=(255.0, 255.0, 255.0)) -> Dict:
+        """A batch for `eval.render_human_frame` from frame `idx`'s OWN camera (stage 2 and 3): the human-object alone over every ray of
+        the frame's box, no scene -- `rays.frame_rays_compact` of `frame_camera(idx)` against `mesh_infos[name]["bbox"]` under the keys of
+        `tpose.tpose_frame` (`img_width`, `img_height`, `ray_mask`, `rays`, `near`, `far`, `pix`, `slot`, `count`, `dst_bbox`,
+        `bgcolor`), and the keys of `frame_pose(idx)`.  The render a body-space frame mesh is scored against (`mesh.fit`)."""
+        cam = self.frame_camera(idx)
+        H, W, E = cam["H"], cam["W"], cam["E"]
+        dev = self.device
+        item = self.frame_pose(idx)
+        r = rays_mod.frame_rays_compact(H, W, cam["K"], E[:3, :3], E[:3, 3], item["dst_bbox"], device=dev)
+        item.update({"img_width": W, "img_height": H, "ray_mask": r["slot"] >= 0, "rays": torch.stack([r["rays_o"], r["rays_d"]], 0),
+                     "near": r["near"][:, None], "far": r["far"][:, None], "pix": r["pix"], "slot": r["slot"], "count": r["count"],
+                     "bgcolor": torch.from_numpy(np.ascontiguousarray(bgcolor, dtype=np.float32)).to(dev)})
+        return item
+
     def eval_frame(self, idx: int, bgcolor=(255.0, 255.0, 255.0)) -> Dict:
         """Frame `idx` seen by its own camera, with the ground-truth pixels (`test_metrics`, model.py:884-1085)."""
         if self.stage != 3:

@@ -170,6 +170,20 @@ def render_frame(hos, frame: Dict, chunk_bkg: int = 8192, randomized: bool = Fal
     return frame_maps if maps else frame_maps["rgb"]                              # M:1311-1313, :1456-1459
 
 
+@contextlib.contextmanager
+def per_sample_outputs(net):
+    """A stage-2 `Network` composites its own samples and returns the maps, not the per-sample radiance (`human_rgbsigma`, `z_vals`,
+    `pts_mask`, `rays_d`) that `render_human_frame` composites itself -- with the same `ops.raw2outputs` arguments, so the colours
+    are the same.  Under `no_grad` its `stage` selects nothing but that return layout, so for the duration of the block it answers
+    as stage 3 does.  A stage-3 network is left as it is."""
+    stage = net.stage
+    net.stage = 3
+    try:
+        yield net
+    finally:
+        net.stage = stage
+
+
 def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = False, median: bool = False):
     """One frame of `test_tpose` (M:614-629): the human-object network alone over every ray of the frame's box, `_raw2outputs`
     over the frame's background colour, no scene.  `frame` is a `tpose.tpose_frame` batch (the reference's T-pose batch plus the
@@ -191,12 +205,13 @@ def render_human_frame(hos, frame: Dict, maps: bool = False, want_u8: bool = Fal
     dev = slot.device
     bgcolor = frame["bgcolor"]
     rgb = acc = depth = med = None
+    human = getattr(hos, "human", hos)                   # a `HOSNeRF`, or the human-object network itself (stage 2's `lit.human`)
     if n > 0:
         per_frame = {k: frame[k] for k in FRAME_KEYS if k in frame}
         per_frame["is_train"] = False
-        with evaluating(hos):
-            pro = hos.human.frame_prologue(**per_frame)
-            out = hos.human(rays=frame["rays"], near=frame["near"], far=frame["far"], prologue=pro, with_cycle=False, **per_frame)
+        with evaluating(hos), per_sample_outputs(human):
+            pro = human.frame_prologue(**per_frame)
+            out = human(rays=frame["rays"], near=frame["near"], far=frame["far"], prologue=pro, with_cycle=False, **per_frame)
             bg = torch.as_tensor(bgcolor, dtype=torch.float32, device=dev)
             if median:
                 m = ops.raw2outputs_median(out["human_rgbsigma"], out["z_vals"], out["rays_d"], out["pts_mask"], bg)

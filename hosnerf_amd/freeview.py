@@ -148,3 +148,32 @@ def save_frame_maps(out_dir: str, name: str, maps: Dict, H: int, W: int) -> Dict
         straight = np.where(ah[..., None] > 0.0, colour / np.where(ah > 0.0, ah, 1.0)[..., None], 0.0)
         Image.fromarray(np.concatenate([to8(straight), to8(ah)[..., None]], -1), mode="RGBA").save(path("human.png"))
     return paths
+
+
+MESH_MAP_FILES = ("_mesh.png", "_mesh_normal.png", "_mesh_mask.png", "_mesh_depth.npy", "_mesh_depth.png")
+
+
+def save_mesh_maps(out_dir: str, name: str, raster: Dict, H: int, W: int) -> Dict[str, str]:
+    """Write the maps of one rasterised mesh (`mesh.rasterize` with `shaded`, `normal`, `mask` and `depth`; tensors or arrays, [H*W]
+    or [H*W,3]) next to its .ply; returns {kind: path}:
+      <name>_mesh.png          the shaded preview (vertex colours under a two-sided head-light, over the background colour), 8-bit RGB
+      <name>_mesh_normal.png   0.5 + 0.5 n of the interpolated normals, 8-bit RGB (grey where empty)
+      <name>_mesh_mask.png     the silhouette, 8-bit greyscale 0 / 255
+      <name>_mesh_depth.npy    float32 [H,W], camera-space z = the ray parameter of the frame's human rays, 0 where empty
+      <name>_mesh_depth.png    `depth_preview` of the covered pixels (near = dark), 0 where empty"""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    to8 = lambda x: (np.clip(x, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    host = lambda k, *c: np.asarray(raster[k].detach().float().cpu() if isinstance(raster[k], torch.Tensor) else raster[k], dtype=np.float32).reshape(H, W, *c)
+    paths = {kind: os.path.join(out_dir, name + kind) for kind in MESH_MAP_FILES}
+    Image.fromarray(to8(host("shaded", 3))).save(paths["_mesh.png"])
+    Image.fromarray(to8(0.5 + 0.5 * host("normal", 3))).save(paths["_mesh_normal.png"])
+    covered = host("mask") != 0
+    Image.fromarray(covered.astype(np.uint8) * 255).save(paths["_mesh_mask.png"])
+    depth = host("depth")
+    np.save(paths["_mesh_depth.npy"], depth)
+    preview = np.zeros((H, W), dtype=np.uint8)
+    if covered.any():
+        preview[covered] = depth_preview(depth[covered])
+    Image.fromarray(preview).save(paths["_mesh_depth.png"])
+    return paths

@@ -238,13 +238,15 @@ def to_space(vertices: torch.Tensor, faces: torch.Tensor, normals, A) -> tuple:
 
 
 def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, space: str = "world", normals: bool = False,
-                  chunk: int = 1 << 18) -> Dict:
+                  chunk: int = 1 << 18, keep_body: bool = False) -> Dict:
     """The mesh of the human-object as it stands in the frame of `pose` (`dataset.SceneItems.frame_pose`): `frame_field`, then
     `ops.march_tets` at `level`.  Returns what `extract` returns (`origin`, `spacing`, `dims` and the field `alpha` / `rgb` are the
     body-frame grid's) plus `space`, `to_world` (float32 [4,4] host array: `pose["newsmpl_to_scale_world"]`, the body frame -> the
     scene's scaled world; the identity for `space="body"`), `normals` (f32 [V,3] or None), `frame_name` and `time`.
     `space="world"` writes the vertices (and turns the normals) by `to_space`; `volume` and `area` are those of the returned
-    vertices.  `level` and `resolution` are unmeasured defaults (module docstring)."""
+    vertices.  `level` and `resolution` are unmeasured defaults (module docstring).  `keep_body=True` adds `body`: the mesh BEFORE
+    `to_space` (`vertices`, `faces`, `colors`, `normals` in the body frame, the space of the frame's rays: what `rasterize` takes
+    with `SceneItems.frame_camera`), the very tensors for `space="body"`; nothing else changes."""
     if space not in SPACES:
         raise ValueError(f"extract_frame: space {space!r} is not one of {SPACES}")
     to_world = np.eye(4, dtype=np.float32)
@@ -257,14 +259,19 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
     field = frame_field(net, pose, resolution, chunk)
     vertices, colors, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"], rgb=field["rgb"])
     vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None
+    colors8 = (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8)
+    body = {"vertices": vertices, "faces": faces, "colors": colors8, "normals": vn} if keep_body else None
     if space == "world":
         vertices, faces, vn = to_space(vertices, faces, vn, to_world)
     volume, area = mesh_measures(vertices, faces)
     time = pose.get("time")
-    return {"vertices": vertices, "faces": faces, "colors": (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
-            "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
-            "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"], "normals": vn, "space": space, "to_world": to_world,
-            "frame_name": pose.get("frame_name"), "time": None if time is None else float(time)}
+    out = {"vertices": vertices, "faces": faces, "colors": colors8, "origin": field["origin"],
+           "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
+           "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"], "normals": vn, "space": space, "to_world": to_world,
+           "frame_name": pose.get("frame_name"), "time": None if time is None else float(time)}
+    if keep_body:
+        out["body"] = body
+    return out
 
 
 # ------------------------------------------------------------------------------------------ the background mesh
@@ -369,3 +376,110 @@ def extract_bkgd(model, box, time: float, resolution: int = 256, level: float = 
             "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
             "level": float(level), "alpha": field["alpha"], "normals": vn if normals else None, "vertex_rgb": rgb,
             "density": field["density"], "var": field["var"], "box": field["box"]}
+
+
+# ------------------------------------------------------------------------------------------ the meshes seen again: raster and fit
+RASTER_MAPS = ("depth", "mask", "face", "rgb", "normal", "shaded")
+FIT_KEYS = ("iou", "area_mesh", "area_ref", "depth_mae", "depth_bias", "depth_rmse", "depth_max")
+
+
+def _pinhole(K):
+    K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
+    if K.shape != (3, 3) or not np.array_equal(K[2], [0.0, 0.0, 1.0]):
+        raise ValueError(f"rasterize: K must be [3,3] with last row (0,0,1) -- only then is the depth of a pixel the ray parameter t; got {K!r}")
+    return K
+
+
+def rasterize(meshes, K, E, H: int, W: int, bgcolor=(255.0, 255.0, 255.0), want=RASTER_MAPS, z_near: float = 1e-6) -> Dict:
+    """One mesh (a dict as `extract` / `extract_frame` / `extract_bkgd` return them: `vertices` f32 [V,3], `faces` int32 [F,3],
+    optionally `colors` uint8 [V,3] and `normals` f32 [V,3]) or a list of them, seen by the camera `K` [3,3] (last row (0,0,1), else
+    `ValueError`), `E` [4,4] or [3,4] (X_cam = E[:3,:3] x + E[:3,3]) in an `H` x `W` frame: the convention of the ray kernels
+    (`rays.frame_rays_compact`, hos_rays.hip), pixel centres at integer coordinates, depth = camera-space z = the ray parameter t of
+    that camera's human rays.  For a frame mesh in body space (`extract_frame(space="body")`, or `keep_body`) the camera is
+    `SceneItems.frame_camera(idx)`; any mesh and camera give pictures.
+
+    All faces go into one z-buffer at consecutive `face_base` values (`ops.mesh_project`, `ops.raster_faces`, `ops.raster_resolve`).
+    Returns the whole-frame device tensors named in `want` -- `depth` f32 [H*W] (0 where empty), `mask` uint8 [H*W], `face` int32
+    [H*W] (-1 where empty), `rgb` [H*W,3] (vertex colours, white without; `bgcolor` / 255 where empty), `normal` [H*W,3] (vertex normals,
+    the faces' own without; 0 where empty), `shaded` [H*W,3] (`rgb` under a two-sided head-light) -- plus `dropped` (int: triangles
+    with a corner behind the camera or past the guard band, or of zero screen area), `face_base` (one int per mesh), `H`, `W`.
+    The read-back of `dropped` is the only host synchronisation."""
+    meshes = [meshes] if isinstance(meshes, dict) else list(meshes)
+    want = tuple(want)
+    if not want or set(want) - set(RASTER_MAPS):
+        raise ValueError(f"rasterize: want {want!r} must name some of {RASTER_MAPS}")
+    K = _pinhole(K)
+    E = np.asarray(E.detach().cpu() if isinstance(E, torch.Tensor) else E, dtype=np.float64)
+    R, T = E[:3, :3], E[:3, 3]
+    H, W = int(H), int(W)
+    n = H * W
+    dev = meshes[0]["vertices"].device if meshes else torch.device("cuda")
+    zbuf = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    dropped = torch.zeros(1, dtype=torch.int32, device=dev)
+    projected, bases, base = [], [], 0
+    for m in meshes:
+        xy, z = ops.mesh_project(m["vertices"].contiguous(), K, R, T, z_near)
+        faces = m["faces"].contiguous()
+        ops.raster_faces(xy, z, faces, base, H, W, zbuf, dropped)
+        projected.append((xy, z, faces))
+        bases.append(base)
+        base += int(faces.shape[0])
+    # the background exactly as `ops.raster_resolve` hands it to the kernel: divided on the host, rounded to fp32 once
+    bg = torch.from_numpy((np.asarray(bgcolor, dtype=np.float64).reshape(3) / 255.0).astype(np.float32)).to(dev)
+    empty = {"depth": lambda: torch.zeros(n, device=dev), "mask": lambda: torch.zeros(n, dtype=torch.uint8, device=dev),
+             "face": lambda: torch.full((n,), -1, dtype=torch.int32, device=dev), "rgb": lambda: bg.expand(n, 3).contiguous(),
+             "normal": lambda: torch.zeros(n, 3, device=dev), "shaded": lambda: bg.expand(n, 3).contiguous()}
+    out = {k: empty[k]() for k in want}                      # what a frame without a single face shows; resolve overwrites the rest
+    Kinv = np.linalg.inv(K)
+    for m, (xy, z, faces), b in zip(meshes, projected, bases):
+        if faces.shape[0] == 0 or xy.shape[0] == 0:
+            continue
+        ops.raster_resolve(zbuf, xy, z, faces, b, H, W, out, vertices=m["vertices"].contiguous(), colors=m.get("colors"),
+                           normals=m.get("normals"), Kinv=Kinv, R=R, bgcolor=bgcolor)
+    out.update(dropped=int(dropped.item()), face_base=bases, H=H, W=W)
+    return out
+
+
+def fit(raster: Dict, alpha, depth=None, tau: float = 0.5, spacing=None) -> Dict:
+    """How well a rasterised mesh (`rasterize` with `mask` and, for the depth figures, `depth`) agrees with a render of the same
+    frame from the same camera: `alpha` [H*W] or [H,W] (the render's opacity, or the scene's subject mask `SceneItems.alphas[idx]`)
+    thresholded at `tau`, `depth` the render's depth in the units of the ray parameter (`depth_median` of
+    `eval.render_human_frame`), or None for the silhouette figures alone.  Returns floats: `iou` (1 when both silhouettes are
+    empty), `area_mesh`, `area_ref` (pixels), and over the pixels both cover `depth_mae`, `depth_bias` (mesh - reference),
+    `depth_rmse`, `depth_max` (0 without a common pixel; absent with `depth=None`); with `spacing` (the mesh's voxel) also
+    `depth_*_vox`, the same in voxels.  One launch pair (`ops.frame_fit`), one read-back.  Defined for the human-object's
+    body-space camera: the background rays' t is not camera z."""
+    mask = raster["mask"].reshape(-1)
+    dev = mask.device
+    as_f32 = lambda x: torch.as_tensor(x).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    alpha = as_f32(alpha)
+    if depth is not None:
+        out = ops.frame_fit(mask, raster["depth"].reshape(-1).contiguous(), alpha, as_f32(depth), tau)
+    else:
+        out = ops.frame_fit(mask, None, alpha, None, tau)
+    host = out.cpu()
+    a, b, ab = (int(c) for c in host[:3].tolist())
+    union = a + b - ab
+    res = {"iou": 1.0 if union == 0 else ab / union, "area_mesh": float(a), "area_ref": float(b)}
+    if depth is not None:
+        s_abs, s, s_sq, mx = (float(x) for x in host[3:].view(torch.float64).tolist())
+        k = max(ab, 1)
+        res.update(depth_mae=s_abs / k, depth_bias=s / k, depth_rmse=math.sqrt(s_sq / k), depth_max=mx)
+        if spacing is not None:
+            res.update({key + "_vox": res[key] / float(spacing) for key in ("depth_mae", "depth_bias", "depth_rmse", "depth_max")})
+    return res
+
+
+def level_sweep(field: Dict, levels, camera: Dict, ref_maps: Dict, tau: float = 0.5):
+    """The instrument for `run.mesh_level`: the already computed `field` (`frame_field`: `alpha`, `rgb`, `origin`, `spacing`) marched
+    again at each of `levels`, rasterised from `camera` (`SceneItems.frame_camera`: `K`, `E`, `H`, `W`) and scored by `fit` against
+    `ref_maps` (`alpha` and `depth_median`, else `depth`: `eval.render_human_frame(maps=True, median=True)` from the same
+    camera).  One row per level: `level`, `V`, `F`, `dropped` and the figures of `fit`, voxel units included.  No network runs."""
+    ref_depth = ref_maps.get("depth_median", ref_maps.get("depth"))
+    rows = []
+    for level in levels:
+        vertices, _, faces = ops.march_tets(field["alpha"], float(level), field["origin"], field["spacing"])
+        r = rasterize({"vertices": vertices, "faces": faces}, camera["K"], camera["E"], camera["H"], camera["W"], want=("depth", "mask"))
+        rows.append({"level": float(level), "V": int(vertices.shape[0]), "F": int(faces.shape[0]), "dropped": r["dropped"],
+                     **fit(r, ref_maps["alpha"], ref_depth, tau=tau, spacing=field["spacing"])})
+    return rows

@@ -2142,3 +2142,88 @@ def march_tets(field, level: float, origin, spacing, rgb=None):
         call("hos_march_tets_write", ptr(field), ptr(rgb), Nx, Ny, Nz, float(level), ox, oy, oz, h, ptr(edge_slot, torch.int32),
              ptr(ws, torch.int32), V, F, ptr(vertices), ptr(colors), ptr(faces, torch.int32))
     return vertices, colors, faces
+
+
+# ------------------------------------------------------------------------------------------ mesh rasteriser (hos_raster.hip)
+def _host_f32(a, shape):
+    """A host array as contiguous fp32 of `shape` plus its pointer (the caller keeps the array alive past the call, which reads it
+    before it returns)."""
+    a32 = np.ascontiguousarray(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64).reshape(shape), dtype=np.float32)
+    return a32, a32.ctypes.data
+
+
+def mesh_project(vertices, K, R, T, z_near: float = 1e-6):
+    """(xy int32 [V,2], z f32 [V]) of `vertices` [V,3] through the camera X_cam = R x + T, (u, v) = (K X_cam).xy / X_cam.z: the screen
+    position in 1/256-pixel fixed point and the camera-space depth; xy[i,0] = INT32_MIN marks a vertex behind `z_near` or outside
+    the guard band of 2^14 pixels (include/hosrender.h).  `K`, `R` [3,3] and `T` [3] are host arrays."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.HosLibraryError(f"mesh_project: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _lib.require_gpu()
+    V = vertices.shape[0]
+    xy = torch.empty(V, 2, dtype=torch.int32, device=vertices.device)
+    z = torch.empty(V, device=vertices.device)
+    k32, kp = _host_f32(K, (9,))
+    r32, rp = _host_f32(R, (9,))
+    t32, tp = _host_f32(T, (3,))
+    call("hos_mesh_project", ptr(vertices) if V else 0, V, kp, rp, tp, float(z_near), ptr(xy, torch.int32) if V else 0, ptr(z) if V else 0)
+    return xy, z
+
+
+def raster_faces(xy, z, faces, face_base: int, H: int, W: int, zbuf, dropped):
+    """The triangles `faces` int32 [F,3] of the projected vertices (`mesh_project`) into `zbuf` int64 [H*W] (filled with -1 by the
+    caller before the first mesh), ids `face_base + f`; `dropped` int32 [1] counts the triangles with an unusable corner or zero
+    area.  Exact integer coverage, top-left rule, one 64-bit atomicMin per covered pixel: deterministic (include/hosrender.h)."""
+    if faces.dim() != 2 or faces.shape[1] != 3 or xy.dim() != 2 or xy.shape[1] != 2 or z.numel() != xy.shape[0]:
+        raise _lib.HosLibraryError(f"raster_faces: faces {tuple(faces.shape)} / xy {tuple(xy.shape)} / z {tuple(z.shape)}")
+    if zbuf.numel() != int(H) * int(W) or dropped.numel() != 1:
+        raise _lib.HosLibraryError(f"raster_faces: zbuf {tuple(zbuf.shape)} does not fit a {H} x {W} frame, or dropped is not [1]")
+    V, F = xy.shape[0], faces.shape[0]
+    call("hos_raster_faces", ptr(xy, torch.int32) if V else 0, ptr(z) if V else 0, V, ptr(faces, torch.int32) if F else 0, F, int(face_base),
+         int(H), int(W), ptr(zbuf, torch.int64), ptr(dropped, torch.int32))
+    return zbuf
+
+
+def raster_resolve(zbuf, xy, z, faces, face_base: int, H: int, W: int, out, vertices=None, colors=None, normals=None, Kinv=None, R=None,
+                   bgcolor=(255.0, 255.0, 255.0)):
+    """The maps of the mesh whose ids are [face_base, face_base + F) from `zbuf`, written in place into the tensors of `out` -- any of
+    `face` int32 [H*W], `depth` f32 [H*W], `mask` uint8 [H*W], `rgb` / `normal` / `shaded` f32 [H*W,3]; empty pixels get the empty
+    values, pixels another mesh won stay untouched (include/hosrender.h).  `colors` uint8 [V,3] (None: white), `normals` f32 [V,3]
+    (None: the faces' geometric normals, from `vertices`); `Kinv`, `R` [3,3] host arrays, needed for `shaded`; `bgcolor` in 0..255."""
+    unknown = set(out) - {"face", "depth", "mask", "rgb", "normal", "shaded"}
+    if unknown or not out:
+        raise _lib.HosLibraryError(f"raster_resolve: outputs {sorted(out)}")
+    n = int(H) * int(W)
+    for k, t in out.items():
+        if t.numel() != n * (3 if k in ("rgb", "normal", "shaded") else 1):
+            raise _lib.HosLibraryError(f"raster_resolve: {k} {tuple(t.shape)} does not fit a {H} x {W} frame")
+    V, F = xy.shape[0], faces.shape[0]
+    for name, t in (("vertices", vertices), ("colors", colors), ("normals", normals)):
+        if t is not None and tuple(t.shape) != (V, 3):
+            raise _lib.HosLibraryError(f"raster_resolve: {name} must be {(V, 3)}, got {tuple(t.shape)}")
+    if zbuf.numel() != n:
+        raise _lib.HosLibraryError(f"raster_resolve: zbuf {tuple(zbuf.shape)} does not fit a {H} x {W} frame")
+    k32, kp = (None, 0) if Kinv is None else _host_f32(Kinv, (9,))
+    r32, rp = (None, 0) if R is None else _host_f32(R, (9,))
+    b32, bp = _host_f32(np.asarray(bgcolor, dtype=np.float64).reshape(3) / 255.0, (3,))
+    call("hos_raster_resolve", ptr(zbuf, torch.int64), ptr(xy, torch.int32) if V else 0, ptr(z) if V else 0, V, ptr(faces, torch.int32) if F else 0,
+         F, int(face_base), ptr(vertices) if V else 0, ptr(colors, torch.uint8) if V else 0, ptr(normals) if V else 0, kp, rp, bp, int(H), int(W),
+         ptr(out.get("face"), torch.int32), ptr(out.get("depth")), ptr(out.get("mask"), torch.uint8), ptr(out.get("rgb")),
+         ptr(out.get("normal")), ptr(out.get("shaded")))
+    return out
+
+
+def frame_fit(mask_a, depth_a, alpha_b, depth_b, tau: float = 0.5) -> torch.Tensor:
+    """One set of maps against another (hos_frame_fit): int64 [7] on the device -- |A|, |B|, |A and B| with A = mask_a != 0 and
+    B = alpha_b > tau, then the bit patterns of four doubles (`out[3:].view(torch.float64)`): over A and B the sums of |dz|, dz, dz^2
+    and the maximum of |dz|, dz = depth_a - depth_b (zeros with both depths None).  Fixed order, sums in double: two runs are
+    bit-equal.  `mask_a` uint8 [n], `alpha_b` / the depths f32 [n]."""
+    n = mask_a.numel()
+    if alpha_b.numel() != n or (depth_a is None) != (depth_b is None) or (depth_a is not None and (depth_a.numel() != n or depth_b.numel() != n)):
+        raise _lib.HosLibraryError("frame_fit: the maps must have one size, and the two depths come together or not at all")
+    _lib.require_gpu()
+    dev = mask_a.device
+    ws = torch.empty(7 * _lib.load().hos_frame_fit_blocks(), dtype=torch.int64, device=dev)
+    out = torch.empty(7, dtype=torch.int64, device=dev)
+    call("hos_frame_fit", ptr(mask_a, torch.uint8) if n else 0, ptr(depth_a) if n else 0, ptr(alpha_b) if n else 0, ptr(depth_b) if n else 0,
+         float(tau), n, ptr(ws, torch.int64), out.data_ptr(), out.data_ptr() + 24)
+    return out

@@ -952,6 +952,53 @@ int hos_march_tets_write(const float* field, const float* rgb, int Nx, int Ny, i
                          const int32_t* edge_slot, const int32_t* ws, int V, int F, float* vertices, float* colors, int32_t* faces,
                          hos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh rasteriser (this build's addition; the reference has no counterpart): a triangle mesh seen through a pin-hole camera with the
+ * convention of hos_camera_rays -- X_cam = R x + T, u = (K X_cam).x / X_cam.z, v = (K X_cam).y / X_cam.z, pixel (col,row) sampled at
+ * (u,v) = (col,row), depth = X_cam.z (the ray parameter t of that camera's rays when K's last row is (0,0,1)).  K9 / Kinv9 / R9 / T3 /
+ * bg01 are HOST pointers, read before the call returns.  Every entry: null pointers / negative sizes HOS_E_ARG, sizes whose ids leave
+ * int32 (V, face_base + F, H*W >= 2^31 - 256) HOS_E_SHAPE, all before any launch; V = 0 or F = 0 is legal and launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+
+/* vertices [V,3] -> xy int32 [V,2] = (lrintf(256 u), lrintf(256 v)), the screen position in 1/256-pixel fixed point, and z [V] = X_cam.z.
+ * xy[i,0] = INT32_MIN (and xy[i,1] = 0) marks a vertex no triangle may use: z <= z_near, z not finite, or |u| or |v| > 2^14 pixels
+ * (the guard band that keeps every integer product of the coverage test inside 64 bits).  z_near >= 0. */
+int hos_mesh_project(const float* vertices, int64_t V, const float* K9, const float* R9, const float* T3, float z_near, int32_t* xy,
+                     float* z, hos_stream_t stream);
+
+/* One thread per triangle of faces int32 [F,3] into zbuf int64 [H*W], which the caller fills with -1 (all ones = empty) before the
+ * first mesh.  A triangle with a corner outside [0,V), an unusable corner or zero area is dropped and counted: dropped[0] += 1 (int32,
+ * zeroed by the caller; integer atomicAdd).  Coverage is exact: 64-bit edge functions of the fixed-point corners at the pixel centres
+ * of the triangle's box clamped to the frame, either orientation (corners 1 and 2 are swapped where the area is negative), top-left
+ * fill rule -- a centre on an edge two triangles of a planar patch share is covered by exactly one of them.  Per covered pixel
+ * b_i = e_i / (e_0 + e_1 + e_2), w_i = b_i * (1 / z_i), depth = 1 / ((w_0 + w_1) + w_2) in fp32, and one 64-bit unsigned atomicMin of
+ * (bits(depth) << 32) | (face_base + f): the nearest surface, at equal depth the lowest id, whatever the launch order.  Several meshes
+ * may share a buffer at disjoint [face_base, face_base + F). */
+int hos_raster_faces(const int32_t* xy, const float* z, int64_t V, const int32_t* faces, int64_t F, int face_base, int H, int W,
+                     int64_t* zbuf, int32_t* dropped, hos_stream_t stream);
+
+/* One thread per pixel.  An empty pixel gets face -1, depth 0, mask 0, rgb = shaded = bg01, normal 0; a pixel whose id lies in
+ * [face_base, face_base + F) gets face = id, depth = the key's depth, mask 1 and, from the winning face's w_i (recomputed as above):
+ *   rgb    [H*W,3]  ((w_0 c_0 + w_1 c_1) + w_2 c_2) * depth / 255 of colors uint8 [V,3]; exactly 1 where colors is NULL
+ *   normal [H*W,3]  the same interpolant of normals [V,3], normalised (scaled by its largest component first), 0 where it vanishes;
+ *                   normals NULL: the face's geometric normal (v1 - v0) x (v2 - v0) of vertices [V,3], in the faces' corner order
+ *   shaded [H*W,3]  rgb * (0.3 + 0.7 |n . d|), d the unit ray direction R^T Kinv [col,row,1] of the pixel (a two-sided head-light)
+ * a pixel another mesh won is left untouched.  Each output pointer may be NULL (not all); vertices is needed only without normals,
+ * Kinv9 / R9 only for shaded. */
+int hos_raster_resolve(const int64_t* zbuf, const int32_t* xy, const float* z, int64_t V, const int32_t* faces, int64_t F, int face_base,
+                       const float* vertices, const unsigned char* colors, const float* normals, const float* Kinv9, const float* R9,
+                       const float* bg01, int H, int W, int32_t* face, float* depth, unsigned char* mask, float* rgb, float* normal,
+                       float* shaded, hos_stream_t stream);
+
+/* One set of maps against another over n pixels: A = mask_a != 0, B = alpha_b > tau;
+ *   counts int64 [3] = |A|, |B|, |A and B|;   sums double [4] = over A and B, with dz = depth_a - depth_b in double:
+ *   sum |dz|, sum dz, sum dz^2, max |dz| (all 0 when depth_a and depth_b are both NULL: the silhouette alone).
+ * Fixed order: per-block partials in ws (int64 [7 * hos_frame_fit_blocks()]), then one final block; no floating-point atomics, so
+ * two runs are bit-equal.  n = 0 writes zeros. */
+int hos_frame_fit_blocks(void);
+int hos_frame_fit(const unsigned char* mask_a, const float* depth_a, const float* alpha_b, const float* depth_b, float tau, int64_t n,
+                  int64_t* ws, int64_t* counts, double* sums, hos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

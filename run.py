@@ -19,6 +19,10 @@ a triangle mesh, <logdir>/mesh/time_<t>.ply + meshes.json (`hosnerf_amd/mesh.py`
 `run.run_mesh_frames` (same stages, same two parameters; this build's addition) writes the POSED human-object of each frame that
 `run.run_eval` would choose (`--eval_skip`), through the renderer's backward warp and in the scene's coordinates,
 <logdir>/mesh_frames/<frame_name>.ply + meshes.json (`mesh.extract_frame`; `run.mesh_space` "world" | "body", `run.mesh_normals` True).
+`run.mesh_preview` (needs `run.run_mesh_frames`; off by default) looks at each of those meshes again through the frame's own camera:
+<frame_name>_mesh.png (shaded), _mesh_normal.png, _mesh_mask.png, _mesh_depth.npy / .png next to the .ply (`mesh.rasterize`,
+hos_raster.hip), and in meshes.json the frame's `fit` against the human-object rendered from that camera (silhouette IoU, depth error
+against `depth_median`) and against the scene's subject mask; `run.mesh_level_sweep = (l0, l1, ...)` adds the same fit per level.
 `run.run_mesh_bkgd` (stages 1 and 3, with `--scene_dir`; this build's addition) writes the BACKGROUND scene of every object state as
 a triangle mesh in the same scaled-world coordinates, <logdir>/mesh_bkgd/time_<t>.ply + meshes.json (`mesh.extract_bkgd`;
 `run.mesh_bkgd_box` (-1,-1,-1, 1,1,1), the same `run.mesh_resolution` / `run.mesh_level`).
@@ -36,6 +40,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -147,6 +152,9 @@ def run(args, gin):
         raise SystemExit("run.run_mesh_frames extracts the posed human-object of each frame (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
     if bool(kw.get("run_mesh_frames", False)) and str(kw.get("mesh_space", "world")) not in ("world", "body"):
         raise SystemExit(f"run.mesh_space = {kw.get('mesh_space')!r}: \"world\" (the scene's coordinates) or \"body\" (the frame's body frame)")
+    if bool(kw.get("mesh_preview", False)) and not bool(kw.get("run_mesh_frames", False)):
+        raise SystemExit("run.mesh_preview = True requires run.run_mesh_frames = True (the preview and the fit are of the frame meshes)")
+    mesh_level_sweep(kw)                              # a malformed sweep stops the run before anything is trained
     if bool(kw.get("run_mesh_bkgd", False)):
         if model_name == "state_humanobject":
             raise SystemExit("run.run_mesh_bkgd extracts the background scene (stage 1 `state_mipnerf360`, stage 3 `hosnerf`); stage 2 has no background model")
@@ -601,26 +609,71 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     (0.5), in `run.mesh_space` ("world": the scene's scaled world, or "body"), with per-vertex normals unless `run.mesh_normals =
     False` -> <logdir>/mesh_frames/<frame_name>.ply and <logdir>/mesh_frames/meshes.json (per frame: time, state, V, F, volume, area,
     level, spacing, dims, space, to_world).  With several ranks the frames are dealt round-robin, each rank writes its own .ply and
-    rank 0 the JSON.  `results.json` is not touched."""
+    rank 0 the JSON.  `results.json` is not touched.
+
+    `run.mesh_preview = True` (opt-in; without it the files and the JSON are exactly the above): every frame's BODY-space mesh --
+    the one extraction, before `mesh.to_space` -- is rasterised from the frame's own camera (`scene.frame_camera`, `mesh.rasterize`)
+    -> <frame_name>_mesh.png / _mesh_normal.png / _mesh_mask.png / _mesh_depth.npy / _mesh_depth.png next to the .ply
+    (`freeview.save_mesh_maps`); the human-object alone is rendered from the same camera (`eval.render_human_frame` of
+    `scene.human_frame`, maps and median depth), and the frame's row gets `fit`: `render` (`mesh.fit` against the render's alpha /
+    depth_median) and `mask` (against the scene's subject mask, silhouette only).  `run.mesh_level_sweep = (l0, l1, ...)` adds
+    `sweep`: `mesh.level_sweep` of the same field against the render, one row per level."""
     from hosnerf_amd import mesh
     load_last(lit, scene, ckpt, "run.run_mesh_frames", "the frames' poses, boxes and cameras")
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
+    preview, sweep = bool(kw.get("mesh_preview", False)), mesh_level_sweep(kw)
     net = lit.human
     idxs = eval_frame_indices(len(scene), args.eval_skip)
+    folder = os.path.join(logdir, "mesh_frames")
 
     def job(j):
         try:
-            m = mesh.extract_frame(net, scene.frame_pose(idxs[j]), resolution=resolution, level=level, space=space, normals=normals)
+            m = mesh.extract_frame(net, scene.frame_pose(idxs[j]), resolution=resolution, level=level, space=space, normals=normals,
+                                   **({"keep_body": True} if preview else {}))          # without the switch: the call as it always was
         except ValueError as e:                      # cameras without smpl_to_scale_world: say so and stop, no half-written sequence
             raise SystemExit(f"run.run_mesh_frames: {e}")
-        return m["frame_name"], m, {"frame_name": m["frame_name"], "time": m["time"], **mesh_measures(m, level), "space": space,
-                                    "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+        row = {"frame_name": m["frame_name"], "time": m["time"], **mesh_measures(m, level), "space": space,
+               "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+        if preview:
+            row.update(preview_frame_mesh(lit, scene, idxs[j], m, folder, sweep))
+        return m["frame_name"], m, row
 
-    rows = write_mesh_set(os.path.join(logdir, "mesh_frames"), len(idxs), rank, world, job, lambda r: r["frame_name"])
+    rows = write_mesh_set(folder, len(idxs), rank, world, job, lambda r: r["frame_name"])
     if rank == 0:
         print(f"[run] frame meshes: {len(idxs)} frames at resolution {resolution}, level {level}, space {space} written to {os.path.join(logdir, 'mesh_frames')}")
     return {"frames": [r["frame_name"] for r in rows], "resolution": resolution, "level": level, "space": space}
+
+
+def mesh_level_sweep(kw):
+    """`run.mesh_level_sweep` = (l0, l1, ...): the levels `run.mesh_preview` re-marches each frame's field at, a tuple of finite
+    floats; absent or empty = no sweep -> tuple."""
+    levels = kw.get("mesh_level_sweep", ())
+    ok = isinstance(levels, (tuple, list)) and all(isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x) for x in levels)
+    if not ok:
+        raise SystemExit(f"run.mesh_level_sweep = {levels!r}: a tuple of finite floats, e.g. (0.1, 0.3, 0.5)")
+    if len(levels) > 0 and not bool(kw.get("mesh_preview", False)):
+        raise SystemExit("run.mesh_level_sweep requires run.mesh_preview = True (the sweep is scored against the preview's render)")
+    return tuple(float(x) for x in levels)
+
+
+def preview_frame_mesh(lit, scene, idx: int, m, folder: str, sweep=()):
+    """`run.mesh_preview` for one frame: the body-space mesh `m["body"]` (`mesh.extract_frame(keep_body=True)`) rasterised from the
+    frame's own camera and written by `freeview.save_mesh_maps` under `folder`, the human-object alone rendered from that camera,
+    and the two compared -> {"fit": {"render": ..., "mask": ...}} and, with `sweep` levels, "sweep": the rows of `mesh.level_sweep`."""
+    from hosnerf_amd import eval as ev, mesh
+    from hosnerf_amd.freeview import save_mesh_maps
+    cam = scene.frame_camera(idx)
+    bgc = tuple(float(c) for c in lit.cfg.bgcolor)
+    raster = mesh.rasterize(m["body"], cam["K"], cam["E"], cam["H"], cam["W"], bgcolor=bgc)
+    save_mesh_maps(folder, m["frame_name"], raster, cam["H"], cam["W"])
+    hos = lit.net if getattr(lit, "net", None) is not None else lit.human     # stage 3: the renderer that owns `human`; stage 2: the network itself
+    render = ev.render_human_frame(hos, scene.human_frame(idx, bgc), maps=True, median=True)
+    out = {"fit": {"render": mesh.fit(raster, render["alpha"], render["depth_median"], spacing=m["spacing"]),
+                   "mask": mesh.fit(raster, scene.alphas[idx])}}
+    if sweep:
+        out["sweep"] = mesh.level_sweep({"alpha": m["alpha"], "origin": m["origin"], "spacing": m["spacing"]}, sweep, cam, render)
+    return out
 
 
 def mesh_bkgd_box(kw):
