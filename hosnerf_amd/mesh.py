@@ -37,7 +37,26 @@ composite for that frame.  The field is taken THROUGH THE BACKWARD WARP, the one
 forward by `lbs_forward` would follow the approximate inverse the cycle loss trains and would not sit where the rendered pixels are.
 The canonical mesh is the special case of identity transforms and no non-rigid offset.  Level 0.5 and resolution 256 are the same
 parameters, as unmeasured on a real scene as they are for the canonical mesh.  Each frame is marched on its own: there is no vertex
-correspondence between frames.
+correspondence between frames -- the tracked mesh below is the counterpart that has it.
+
+The tracked mesh (`track`): ONE topology per object state, posed per frame.  The template is the canonical mesh of the state
+(`extract`); for a frame of that state every template vertex c is carried to the body-frame point p with
+
+    G(p) = nonrigid(x_skel(p)) = c              # x_skel: the frame's backward LBS, the map the renderer samples through
+
+i.e. the renderer's backward map is INVERTED per vertex, not replaced by `lbs_forward` (which only supplies the first guess).  The
+rigid part x_skel(p) = c - delta is solved by Newton's method on the trilinear motion-weight volume with the analytic Jacobian
+(`ops.warp_invert`, hos_track.hip), the non-rigid offset delta = G(p) - x_skel(p) by a plain fixed point around it (`outer` rounds).
+That fixed point converges where the offset is a contraction (small against a voxel of the volume, as the reference initialises it);
+an offset field that folds space (det(I + d offset / dx) <= 0) has no inverse, and nothing converges on it.  Whether a trained
+scene stays in the convergent regime is unmeasured: `residual` and `converged` are returned per vertex so that it can be seen.
+What the tracked surface is: on the template alpha_c(c) = mask_c(c) (1 - exp(-sigma h)) = level; at the tracked point the frame's
+field is mask(p) (1 - exp(-sigma h)) = level * mask(p) / mask_c(c).  So a tracked vertex lies on the frame's own isosurface exactly
+where the posed and the canonical mask agree; `mask` and `mask_canonical` are both returned so that their ratio can be seen.
+Tracking is per object state: the states have different canonical fields, hence different templates and no correspondence across
+a transition.  Tracked normals (`normals=True`) are the normalised J^T n_c, J = d x_skel / dp at p and n_c the template's normal: the
+pull-back of the canonical field's gradient through the rigid warp -- this NEGLECTS the Jacobian of the non-rigid offset and the
+gradient of the mask ratio above.
 
 Normals (`normals=True`, both meshes): per vertex the normalised negative central difference, step h, of the field's trilinear
 interpolant (`ops.mesh_vertex_normals`), so they follow the field the surface was cut from and need no face adjacency.
@@ -272,6 +291,125 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
     if keep_body:
         out["body"] = body
     return out
+
+
+# ------------------------------------------------------------------------------------------ the tracked mesh
+def _padded_rows(x: torch.Tensor, rows: int) -> torch.Tensor:
+    """`x` [n,...] repeated from its first row on up to `rows` rows (n >= 1), so that a short template still runs the MLP on the
+    thin kernels; the copies are computed and dropped."""
+    n = x.shape[0]
+    if n >= rows:
+        return x.contiguous()
+    return x[torch.arange(rows, device=x.device) % n].contiguous()
+
+
+def track(net, template: Dict, pose: Dict, outer: int = 6, iters: int = 4, tol=None, space: str = "world", normals: bool = False,
+          chunk: int = 1 << 18) -> Dict:
+    """The canonical mesh `template` (what `extract` returned for the object state of `pose`'s time) posed into the frame of `pose`
+    (`dataset.SceneItems.frame_pose`) VERTEX BY VERTEX: for every template vertex c the body-frame point p with G(p) = c, G the
+    renderer's backward map of the frame (module docstring, "The tracked mesh").  `outer` rounds of the fixed point, each one
+    `ops.warp_invert` of at most `iters` Newton steps (tolerance `tol` / 4, steps of at most one voxel of the motion-weight volume)
+    and one non-rigid chain; `tol` defaults to 1e-3 * template["spacing"].  Under `evaluating`, `no_grad` and `ops.guarded_forward`;
+    one `frame_prologue` per call (`is_train` False, `iter_val` 1e7 unless given, as `frame_field`); per chunk of `chunk` >= 16384
+    vertices (the last one moved back; a shorter template is padded with copies of its own rows).
+
+    Returns `vertices` f32 [V,3] in `space` ("world" through `to_space`, as `extract_frame`; `to_world` likewise), `faces` and
+    `colors`: the TEMPLATE's own tensors (faces flipped by `to_space` where it mirrors), `residual` f32 [V] = |G(p) - c|_2,
+    `converged` bool [V] (the last inner solve converged, residual <= tol, never lost), `mask` f32 [V] (the posed mask at p),
+    `mask_canonical` f32 [V] (the template's own mask at c), `cnl` f32 [V,3] (the device's G(p)), `normals` (f32 [V,3] with
+    `normals=True`, which needs the template's; else None), `state`, `frame_name`, `time`, `volume`, `area` (of the returned
+    vertices), `tol`, `space`, `to_world` and the template's `level`, `spacing`, `dims`.  A vertex that is lost in some round (no
+    motion weight, a singular Jacobian, a non-finite residual) keeps its last finite p and is not converged."""
+    if space not in SPACES:
+        raise ValueError(f"track: space {space!r} is not one of {SPACES}")
+    if pose.get("time") is None:
+        raise ValueError("track: pose has no `time` (the object state of the frame is selected by it)")
+    state = select_state(float(pose["time"]), net.transitions_times)
+    if int(template["state"]) != int(state):
+        raise ValueError(f"track: the template is of object state {int(template['state'])}, the frame at time {float(pose['time'])} of state "
+                         f"{int(state)}: the states have different canonical fields, a template tracks within its own state only")
+    if normals and template.get("normals") is None:
+        raise ValueError("track: normals=True needs a template with normals (`extract(..., normals=True)`)")
+    outer, iters, chunk = int(outer), int(iters), int(chunk)
+    if outer < 1 or iters < 0:
+        raise ValueError(f"track: outer {outer} < 1 or iters {iters} < 0")
+    if chunk < THIN_ROWS:
+        raise ValueError(f"track: chunk {chunk} < {THIN_ROWS} rows (the thin kernels' lower bound)")
+    tol = 1e-3 * float(template["spacing"]) if tol is None else float(tol)
+    if not tol > 0:
+        raise ValueError(f"track: tol {tol} must be positive")
+    to_world = np.eye(4, dtype=np.float32)
+    if space == "world":
+        if pose.get("newsmpl_to_scale_world") is None:
+            raise ValueError("track: space=\"world\" needs pose[\"newsmpl_to_scale_world\"], which this scene's cameras do not "
+                             "give (no `smpl_to_scale_world`); use space=\"body\"")
+        A = pose["newsmpl_to_scale_world"]
+        to_world = np.ascontiguousarray(A.detach().cpu().numpy() if hasattr(A, "detach") else A, dtype=np.float32).reshape(4, 4)
+    c_all = template["vertices"]
+    dev = c_all.device
+    V = int(c_all.shape[0])
+    bmin, bscale = pose["cnl_bbox_min_xyz"].contiguous(), pose["cnl_bbox_scale_xyz"].contiguous()
+    per_frame = {k: pose[k] for k in FRAME_KEYS if k in pose}
+    per_frame["is_train"] = False
+    per_frame.setdefault("iter_val", 1e7)
+    K = int(net.cfg.total_bones)
+    out = {"p": torch.zeros(V, 3, device=dev), "cnl": torch.full((V, 3), float("nan"), device=dev), "mask": torch.zeros(V, device=dev),
+           "mask_canonical": torch.zeros(V, device=dev), "residual": torch.full((V,), float("inf"), device=dev),
+           "converged": torch.zeros(V, dtype=torch.bool, device=dev), "jac": torch.zeros(V, 3, 3, device=dev) if normals else None}
+
+    def run():
+        pro = net.frame_prologue(**per_frame)                                                # once per call
+        vol = pro["vol"]
+        max_step = 2.0 / float(bscale.min()) / (int(vol.shape[-1]) - 1)                      # one voxel: longest box extent / (V - 1)
+        eye, zero = torch.eye(3, device=dev).expand(K, 3, 3).contiguous(), torch.zeros(K, 3, device=dev)
+        padded = _padded_rows(c_all, THIN_ROWS)
+        n = padded.shape[0]
+        rows = min(chunk, n)
+        for c0 in range(0, n, rows):
+            first = min(c0, n - rows)
+            c = padded[first:first + rows].contiguous()
+            p = ops.lbs_forward(c, pro["R_f"], pro["T_f"], pro["vol_cl"], bmin, bscale, K)
+            delta = torch.zeros_like(c)
+            alive = torch.ones(rows, dtype=torch.bool, device=dev)
+            status = torch.full((rows,), ops.TRACK_LOST, dtype=torch.int32, device=dev)
+            cnl, mask, res = torch.full_like(c, float("nan")), torch.zeros(rows, device=dev), torch.full((rows,), float("inf"), device=dev)
+            for _ in range(outer):
+                p_o, x_o, m_o, _, st_o = ops.warp_invert(c - delta, p, pro["R_b"], pro["T_b"], vol, bmin, bscale, K=K, iters=iters,
+                                                         tol=tol / 4.0, max_step=max_step)
+                cnl_o, _ = net._nonrigid_fwd(net._nr, x_o, pro["cond"], pro["band_w"], save=False)
+                ok = alive & torch.isfinite(p_o).all(dim=1)                                  # a frozen row, or a step that blew up: keep
+                ok3 = ok[:, None]
+                p, cnl, delta = torch.where(ok3, p_o, p), torch.where(ok3, cnl_o, cnl), torch.where(ok3, cnl_o - x_o, delta)
+                mask, res = torch.where(ok, m_o, mask), torch.where(ok, (cnl_o - c).norm(dim=1), res)
+                status = torch.where(ok, st_o, status)
+                alive = ok & (st_o != ops.TRACK_LOST)
+            live = slice(0, max(0, min(rows, V - first)))                                    # the rows that are template vertices
+            dst = slice(first, first + live.stop)
+            out["p"][dst], out["cnl"][dst], out["mask"][dst], out["residual"][dst] = p[live], cnl[live], mask[live], res[live]
+            out["converged"][dst] = (alive & (status == ops.TRACK_CONVERGED) & (res <= tol))[live]
+            out["mask_canonical"][dst] = ops.warp_invert(c, c, eye, zero, vol, bmin, bscale, K=K, iters=0, tol=tol, max_step=max_step)[2][live]
+            if normals:
+                out["jac"][dst] = ops.warp_invert(c, p.contiguous(), pro["R_b"], pro["T_b"], vol, bmin, bscale, K=K, iters=0, tol=tol,
+                                                  max_step=max_step, want_jac=True)[5][live]
+
+    if V > 0:
+        with evaluating(net):
+            ops.guarded_forward(net, dev, run)
+    vn = None
+    if normals:
+        n = torch.einsum("vab,va->vb", out["jac"].double(), template["normals"].double())    # J^T n_c: the gradient pulled back
+        length = n.norm(dim=1, keepdim=True)
+        vn = torch.where(torch.isfinite(length) & (length > 0), n / length.clamp_min(1e-300), torch.zeros_like(n)).float()
+    vertices, faces = out["p"], template["faces"]
+    if space == "world":
+        vertices, faces, vn = to_space(vertices, faces, vn, to_world)
+    volume, area = mesh_measures(vertices, faces)
+    time = float(pose["time"])
+    return {"vertices": vertices, "faces": faces, "colors": template["colors"], "normals": vn, "residual": out["residual"],
+            "converged": out["converged"], "mask": out["mask"], "mask_canonical": out["mask_canonical"], "cnl": out["cnl"],
+            "state": int(state), "frame_name": pose.get("frame_name"), "time": time, "volume": volume, "area": area, "tol": tol,
+            "space": space, "to_world": to_world, "level": template.get("level"), "spacing": float(template["spacing"]),
+            "dims": template["dims"]}
 
 
 # ------------------------------------------------------------------------------------------ the background mesh

@@ -2072,6 +2072,33 @@ def grid_warp(R_b, T_b, vol, bbox_min, bbox_scale, origin, spacing, dims, first:
     return x_skel, mask
 
 
+TRACK_CONVERGED, TRACK_LIMIT, TRACK_LOST = 0, 1, 2          # the row status of `warp_invert` (hos_track.hip)
+
+
+def warp_invert(target, guess, R_b, T_b, vol, bbox_min, bbox_scale, K: int = 26, iters: int = 4, tol: float = 1e-5, max_step: float = 0.1,
+                want_jac: bool = False):
+    """The backward LBS of `grid_warp` inverted per row: Newton's method on x_skel(p) = `target` [P,3] from `guess` [P,3], at most
+    `iters` steps of length <= `max_step`, until |target - x_skel(p)|_2 <= `tol` (include/hosrender.h, "The tracked mesh") ->
+    (p [P,3], x_skel [P,3], mask [P], residual [P], status int32 [P]: 0 converged, 1 out of steps, 2 lost[, jac [P,3,3] = dx_skel/dp
+    with `want_jac`]), everything evaluated at the returned p.  `iters=0` is a plain point warp with its Jacobian.  P = 0 returns
+    empty tensors without a launch."""
+    _lib.require_gpu()
+    if (tuple(R_b.shape) != (K, 3, 3) or tuple(T_b.shape) != (K, 3) or vol.dim() != 4 or vol.shape[0] < K or target.dim() != 2
+            or target.shape[1] != 3 or tuple(guess.shape) != tuple(target.shape)):
+        raise _lib.HosLibraryError(f"warp_invert: target {tuple(target.shape)} / guess {tuple(guess.shape)} / R_b {tuple(R_b.shape)} / "
+                                   f"T_b {tuple(T_b.shape)} / vol {tuple(vol.shape)} do not fit K = {K}")
+    dev = vol.device
+    P = int(target.shape[0])
+    p, x_skel = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
+    mask, residual = torch.empty(P, device=dev), torch.empty(P, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    jac = torch.empty(P, 3, 3, device=dev) if want_jac else None
+    if P > 0:
+        call("hos_warp_invert", ptr(target), ptr(guess), ptr(R_b), ptr(T_b), ptr(vol), vol.shape[-1], K, ptr(bbox_min), ptr(bbox_scale),
+             int(iters), float(tol), float(max_step), P, ptr(p), ptr(x_skel), ptr(mask), ptr(residual), ptr(status, torch.int32), ptr(jac))
+    return (p, x_skel, mask, residual, status) + ((jac,) if want_jac else ())
+
+
 def grid_alpha_masked(raw, mask, origin, spacing, dims, first: int, alpha, rgb=None):
     """`grid_alpha` with the mask given: alpha[first + r] = mask[r] * (1 - exp(-raw[r,3] * spacing)), 0 on the grid's outermost layer;
     rgb[first + r] = raw[r,:3] when given.  `raw` [count,4], `mask` [count] (of `grid_warp`); `alpha` / `rgb` are whole-grid tensors."""

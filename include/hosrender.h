@@ -999,6 +999,30 @@ int hos_frame_fit_blocks(void);
 int hos_frame_fit(const unsigned char* mask_a, const float* depth_a, const float* alpha_b, const float* depth_b, float tau, int64_t n,
                   int64_t* ws, int64_t* counts, double* sums, hos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The tracked mesh (this build's addition; the reference has no counterpart): the backward LBS of hos_grid_warp INVERTED per point,
+ * so that the canonical mesh of an object state can be posed into a frame vertex by vertex, through the warp the renderer samples.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Per row r of P: Newton's method on x(p) = target[r], started at guess[r].  x(p), W(p) are hos_grid_warp's x_skel and mask at the
+ * body-frame point p (q_i = (R_b[i] p) + T_b[i], w_i = zero-padded trilinear tap of vol channel i, A = sum w_i q_i, W = sum w_i,
+ * x = A / max(W, 1e-4)), and J = dx/dp = (sum_i (q_i (x) g_i + w_i R_b[i]) - x (x) sum_i g_i) / W with g_i = R_b[i]^T grad_q w_i;
+ * grad_q w_i is the gradient of the trilinear interpolant inside the cell of floor (one-sided on a cell face; taps outside the
+ * volume zero as in the value), times bbox_scale[a] * (V - 1) / 2 per axis; value and gradient come from the same eight loads.
+ * (Where W <= 1e-4 the clamp makes the denominator constant, J = sum_i (...) / 1e-4; such a row is LOST anyway.)
+ *   p = guess;  for it = 0, 1, ...:  evaluate x, W, J at p;  r = target - x;
+ *       r not finite or W <= 1e-4 -> status 2 (LOST), stop;   |r|_2 <= tol -> status 0 (CONVERGED), stop;
+ *       it == iters -> status 1 (LIMIT), stop;                !(|det J| > 1e-12) -> status 2 (LOST), stop;
+ *       d = J^-1 r (adjugate / det), scaled to length max_step where longer;  p += d
+ * Outputs, all AT THE RETURNED p: p_out [P,3], x_skel [P,3] = x(p), mask [P] = W(p), residual [P] = |r|_2, status int32 [P], and
+ * jac [P,9] = J(p) row-major [out][in] when jac != NULL.  iters = 0 is a plain point warp with its Jacobian (p_out = guess).
+ * R_b [K,3,3], T_b [K,3], vol [>=K,V,V,V]; bbox_min / bbox_scale [3] of the CANONICAL box.  fp32, one row per thread, no atomics,
+ * rows indexed in 64 bits; a row depends on its own inputs only.  HOS_E_ARG: a null pointer other than jac, P <= 0, iters < 0, tol or
+ * max_step not > 0;  HOS_E_SHAPE: V < 2, K outside 1..32, P > 256 * (2^31 - 1); all before any launch. */
+int hos_warp_invert(const float* target, const float* guess, const float* R_b, const float* T_b, const float* vol, int V, int K,
+                    const float* bbox_min, const float* bbox_scale, int iters, float tol, float max_step, int64_t P, float* p_out,
+                    float* x_skel, float* mask, float* residual, int32_t* status, float* jac, hos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

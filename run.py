@@ -23,6 +23,11 @@ a triangle mesh, <logdir>/mesh/time_<t>.ply + meshes.json (`hosnerf_amd/mesh.py`
 <frame_name>_mesh.png (shaded), _mesh_normal.png, _mesh_mask.png, _mesh_depth.npy / .png next to the .ply (`mesh.rasterize`,
 hos_raster.hip), and in meshes.json the frame's `fit` against the human-object rendered from that camera (silhouette IoU, depth error
 against `depth_median`) and against the scene's subject mask; `run.mesh_level_sweep = (l0, l1, ...)` adds the same fit per level.
+`run.run_mesh_track` (stages 2 and 3, with `--scene_dir`; this build's addition) writes the TRACKED human-object: per object state
+the canonical mesh as a template, and for each frame `run.run_eval` would choose that template posed vertex by vertex through the
+inverted backward warp -- one topology per state -- <logdir>/mesh_track/template_state_<s>.ply, <frame_name>.ply,
+<frame_name>_residual.npy + meshes.json (`mesh.track`; the same `run.mesh_resolution` / `run.mesh_level` / `run.mesh_space` /
+`run.mesh_normals`).
 `run.run_mesh_bkgd` (stages 1 and 3, with `--scene_dir`; this build's addition) writes the BACKGROUND scene of every object state as
 a triangle mesh in the same scaled-world coordinates, <logdir>/mesh_bkgd/time_<t>.ply + meshes.json (`mesh.extract_bkgd`;
 `run.mesh_bkgd_box` (-1,-1,-1, 1,1,1), the same `run.mesh_resolution` / `run.mesh_level`).
@@ -150,7 +155,9 @@ def run(args, gin):
         raise SystemExit("run.run_mesh extracts the canonical human-object (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
     if bool(kw.get("run_mesh_frames", False)) and model_name == "state_mipnerf360":
         raise SystemExit("run.run_mesh_frames extracts the posed human-object of each frame (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
-    if bool(kw.get("run_mesh_frames", False)) and str(kw.get("mesh_space", "world")) not in ("world", "body"):
+    if bool(kw.get("run_mesh_track", False)) and model_name == "state_mipnerf360":
+        raise SystemExit("run.run_mesh_track poses the canonical human-object into each frame (stage 2 `state_humanobject`, stage 3 `hosnerf`); stage 1 has no human-object network")
+    if (bool(kw.get("run_mesh_frames", False)) or bool(kw.get("run_mesh_track", False))) and str(kw.get("mesh_space", "world")) not in ("world", "body"):
         raise SystemExit(f"run.mesh_space = {kw.get('mesh_space')!r}: \"world\" (the scene's coordinates) or \"body\" (the frame's body frame)")
     if bool(kw.get("mesh_preview", False)) and not bool(kw.get("run_mesh_frames", False)):
         raise SystemExit("run.mesh_preview = True requires run.run_mesh_frames = True (the preview and the fit are of the frame meshes)")
@@ -348,6 +355,8 @@ def run(args, gin):
         result["mesh"] = extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world)
     if bool(kw.get("run_mesh_frames", False)):
         result["mesh_frames"] = extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world)
+    if bool(kw.get("run_mesh_track", False)):
+        result["mesh_track"] = track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world)
     if bool(kw.get("run_mesh_bkgd", False)):
         result["mesh_bkgd"] = extract_bkgd_meshes(kw, lit, model_name, scene if bank is None else bank, ckpt, logdir, dev, rank, world)
     if world > 1:
@@ -643,6 +652,73 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     if rank == 0:
         print(f"[run] frame meshes: {len(idxs)} frames at resolution {resolution}, level {level}, space {space} written to {os.path.join(logdir, 'mesh_frames')}")
     return {"frames": [r["frame_name"] for r in rows], "resolution": resolution, "level": level, "space": space}
+
+
+def _spread(x):
+    """{median, p99, max} of a device vector as floats (empty: zeros)."""
+    x = x.double()
+    if x.numel() == 0:
+        return {"median": 0.0, "p99": 0.0, "max": 0.0}
+    return {"median": float(x.median()), "p99": float(torch.quantile(x, 0.99)), "max": float(x.max())}
+
+
+def track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
+    """`run.run_mesh_track` (this build's addition; stage 2 and stage 3): the human-object as ONE mesh per object state that moves
+    -- the canonical mesh of the state (`mesh.extract` at the state's time of `tpose.tpose_times`, `run.mesh_resolution` (256),
+    `run.mesh_level` (0.5), with normals unless `run.mesh_normals = False`) posed into every frame `run.run_eval` chooses
+    (`--eval_skip`, else eight over the sequence) by `mesh.track`, in `run.mesh_space` -> <logdir>/mesh_track/template_state_<s>.ply
+    per state, <frame_name>.ply (the template's faces and colours, the frame's vertices) and <frame_name>_residual.npy (float32 [V],
+    |G(p) - c| per vertex) per frame, and meshes.json (per frame: frame_name, time, state, template, V, F, converged (share),
+    residual {median, p99, max}, mask_ratio {median, min, max} of mask / mask_canonical over the vertices whose canonical mask exceeds 1e-4,
+    volume, area, level, spacing, dims, space, to_world).  The templates are extracted once per state on every rank that needs them;
+    the frames are dealt round-robin, each rank writes its own files and rank 0 the JSON (and the templates).  `results.json` is not
+    touched."""
+    import numpy as np
+    from hosnerf_amd import formats, mesh, tpose
+    load_last(lit, scene, ckpt, "run.run_mesh_track", "the frames' poses and the canonical joints and box")
+    resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
+    space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
+    net = lit.human
+    turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
+    state_time = {mesh.select_state(float(t), net.transitions_times): float(t) for t in tpose.tpose_times(net.transitions_times)}
+    idxs = eval_frame_indices(len(scene), args.eval_skip)
+    folder = os.path.join(logdir, "mesh_track")
+    os.makedirs(folder, exist_ok=True)
+    templates = {}
+
+    def template_of(state):
+        if state not in templates:
+            templates[state] = mesh.extract(net, turn, state_time[state], resolution=resolution, level=level, normals=normals)
+        return templates[state]
+
+    def job(j):
+        pose = scene.frame_pose(idxs[j])
+        tpl = template_of(mesh.select_state(float(pose["time"]), net.transitions_times))
+        try:
+            m = mesh.track(net, tpl, pose, space=space, normals=normals)
+        except ValueError as e:                      # cameras without smpl_to_scale_world: say so and stop
+            raise SystemExit(f"run.run_mesh_track: {e}")
+        np.save(os.path.join(folder, m["frame_name"] + "_residual.npy"), m["residual"].cpu().numpy().astype(np.float32))
+        on = m["mask_canonical"] > 1e-4                 # the solver's own weight threshold: below it a vertex is lost by definition
+        ratio = (m["mask"][on] / m["mask_canonical"][on]).double()
+        row = {"frame_name": m["frame_name"], "time": m["time"], "state": m["state"], "template": f"template_state_{m['state']}.ply",
+               "V": int(m["vertices"].shape[0]), "F": int(m["faces"].shape[0]),
+               "converged": float(m["converged"].double().mean()) if m["converged"].numel() else 0.0, "residual": _spread(m["residual"]),
+               "mask_ratio": {"median": float(ratio.median()), "min": float(ratio.min()), "max": float(ratio.max())} if ratio.numel()
+               else {"median": 0.0, "min": 0.0, "max": 0.0},
+               "volume": m["volume"], "area": m["area"], "level": level, "spacing": m["spacing"], "dims": list(m["dims"]), "space": space,
+               "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+        return m["frame_name"], m, row
+
+    rows = write_mesh_set(folder, len(idxs), rank, world, job, lambda r: r["frame_name"])
+    if rank == 0:                                    # every object state, extracted here if this rank met none of its frames
+        for s in sorted(state_time):
+            t = template_of(s)
+            formats.write_ply(os.path.join(folder, f"template_state_{s}.ply"), t["vertices"], t["faces"], t["colors"], t.get("normals"))
+        print(f"[run] tracked meshes: {len(idxs)} frames of {len({r['state'] for r in rows})} object states at resolution {resolution}, "
+              f"level {level}, space {space} written to {folder}")
+    return {"frames": [r["frame_name"] for r in rows], "states": sorted({r["state"] for r in rows}), "resolution": resolution, "level": level,
+            "space": space}
 
 
 def mesh_level_sweep(kw):
