@@ -3,7 +3,8 @@
 // hos_encode_ipe: conical-frustum moments (H:294-304) -> full-covariance lift (H:318-339) ->
 // scene contraction with closed-form Jacobian (H:33-68; SURVEY 7.1: equals functorch.jacrev to
 // 1.5e-8) -> projection on the 21-direction icosahedron basis (H:71-74) -> integrated positional
-// encoding (H:78-89) -> [IPE(504) | state embedding(64) | 0-pad] rows ready for the layer-0 GEMM.
+// encoding (H:78-89) -> [IPE(504) | state embedding(64) | 0-pad] rows ready for the layer-0 GEMM, or (embed = NULL)
+// [IPE(504) | 0-pad] rows for an MLP that takes the embedding as a bias.
 // In the reference this is ~40 torch launches with [B,S,3,3] / [B,S,12,21] temporaries and a
 // vmap(jacrev) autograd pass (13.5 % + 18 % of its forward time).
 //
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
     const long p0 = (long)blockIdx.x * SB;
     if (t < 3 * NDIR) s_basis[t / NDIR][t % NDIR] = basis[t];
     if (t == 255) s_big = 0;
-    if (t >= 64 && t < 64 + NEMB) s_embed[t - 64] = embed[t - 64];
+    if (t >= 64 && t < 64 + NEMB) s_embed[t - 64] = embed != nullptr ? embed[t - 64] : 0.f;     // no embedding: the tail is all zeros
 
     if (t < SB) {
         if (p0 + t < P) {
@@ -319,13 +320,18 @@ __global__ __launch_bounds__(256) void encode_viewdirs_kernel(const float* __res
     }
 }
 
+// Narrowest row an entry point accepts.  embed == NULL selects the row form without the state embedding, [IPE(504) | 0 ...]: the
+// MLPs then take the embedding as a per-call bias (hos_embed_bias_fold) and their layer-0 / skip operand is 512 columns = 16 K
+// tiles of the planes GEMMs instead of 576 = 18.  Columns [0, 504) do not depend on the choice (same loop, same order).
+inline int row_min(const float* embed) { return embed != nullptr ? NIPE + NEMB : NIPE; }
+
 }  // namespace
 
 extern "C" int hos_encode_ipe(const float* tdist, const float* rays_o, const float* rays_d, const float* radii,
                               const float* basis, const float* embed, int B, int S, float* X, int ldx,
                               hos_stream_t stream) {
-    if (!tdist || !rays_o || !rays_d || !radii || !basis || !embed || !X || B <= 0 || S <= 0) return HOS_E_ARG;
-    if (ldx < NIPE + NEMB) return HOS_E_SHAPE;
+    if (!tdist || !rays_o || !rays_d || !radii || !basis || !X || B <= 0 || S <= 0) return HOS_E_ARG;
+    if (ldx < row_min(embed)) return HOS_E_SHAPE;
     const long P = (long)B * S;
     hipLaunchKernelGGL((encode_ipe_kernel<false, FrustumStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), FrustumStage{tdist, rays_o, rays_d, radii, S}, basis, embed, P, X, ldx,
@@ -336,8 +342,8 @@ extern "C" int hos_encode_ipe(const float* tdist, const float* rays_o, const flo
 extern "C" int hos_encode_ipe_planes(const float* tdist, const float* rays_o, const float* rays_d, const float* radii,
                                      const float* basis, const float* embed, int B, int S, void* p16, void* pb, int ld,
                                      hos_stream_t stream) {
-    if (!tdist || !rays_o || !rays_d || !radii || !basis || !embed || (!p16 && !pb) || B <= 0 || S <= 0) return HOS_E_ARG;
-    if (ld < NIPE + NEMB || (ld & 31)) return HOS_E_SHAPE;
+    if (!tdist || !rays_o || !rays_d || !radii || !basis || (!p16 && !pb) || B <= 0 || S <= 0) return HOS_E_ARG;
+    if (ld < row_min(embed) || (ld & 31)) return HOS_E_SHAPE;
     const long P = (long)B * S;
     hipLaunchKernelGGL((encode_ipe_kernel<true, FrustumStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), FrustumStage{tdist, rays_o, rays_d, radii, S}, basis, embed, P, (float*)nullptr, ld,
@@ -348,8 +354,8 @@ extern "C" int hos_encode_ipe_planes(const float* tdist, const float* rays_o, co
 // The grid of 64-row workgroups is one 32-bit dimension: P <= 64 * (2^31 - 1) rows (a 5000^3 grid), HOS_E_SHAPE beyond.
 extern "C" int hos_encode_ipe_points(const float* pts, int64_t P, float var, const float* basis, const float* embed, float* X, int ldx,
                                      hos_stream_t stream) {
-    if (!pts || !basis || !embed || !X || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
-    if (ldx < NIPE + NEMB || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
+    if (!pts || !basis || !X || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
+    if (ldx < row_min(embed) || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
     hipLaunchKernelGGL((encode_ipe_kernel<false, PointStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), PointStage{pts, var}, basis, embed, (long)P, X, ldx,
                        (unsigned short*)nullptr, (unsigned short*)nullptr);
@@ -358,8 +364,8 @@ extern "C" int hos_encode_ipe_points(const float* pts, int64_t P, float var, con
 
 extern "C" int hos_encode_ipe_points_planes(const float* pts, int64_t P, float var, const float* basis, const float* embed, void* p16,
                                             void* pb, int ld, hos_stream_t stream) {
-    if (!pts || !basis || !embed || (!p16 && !pb) || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
-    if (ld < NIPE + NEMB || (ld & 31) || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
+    if (!pts || !basis || (!p16 && !pb) || P <= 0 || !(var >= 0.f)) return HOS_E_ARG;
+    if (ld < row_min(embed) || (ld & 31) || (P + SB - 1) / SB > 0x7fffffffL) return HOS_E_SHAPE;
     hipLaunchKernelGGL((encode_ipe_kernel<true, PointStage>), dim3((unsigned)((P + SB - 1) / SB)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), PointStage{pts, var}, basis, embed, (long)P, (float*)nullptr, ld,
                        (unsigned short*)p16, (unsigned short*)pb);

@@ -47,10 +47,20 @@ __global__ __launch_bounds__(1024) void any_abs_below_kernel(const float* __rest
 // its gradient is the bias gradient through its columns of the weight (M:295-296, N:177-230).  One workgroup of 16 waves, each
 // walking every 16th row with eight loads in flight (the first version -- 4 waves, one dependent load per iteration over 256
 // rows -- took 136 us per call for 256 KB: pure latency); fixed summation order.
+//
+// embed != NULL (the MLP took the embedding as a bias, hos_embed_bias_fold, so no GEMM saw its columns): workgroups 1.. add the
+// weight gradient of those columns, dW[n][c0 + e] += db[n] embed[e] -- what dZ^T X gives on 64 columns of X that are the same in
+// every row.  16 rows per workgroup, one element per thread, each written by exactly one thread (no atomics, nothing to order).
 __global__ __launch_bounds__(1024) void state_embed_grad_kernel(const float* __restrict__ db, const float* __restrict__ W, int ldw, int c0, int N,
-                                                                int E, float* __restrict__ gb, float* __restrict__ g_embed) {
+                                                                int E, float* __restrict__ gb, float* __restrict__ g_embed,
+                                                                const float* __restrict__ embed, float* __restrict__ dW, int lddw) {
     __shared__ float part[16][64];
     const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
+    if (blockIdx.x > 0) {
+        const int n = ((int)blockIdx.x - 1) * 16 + q;
+        if (n < N && e < E) dW[(size_t)n * lddw + c0 + e] += db[n] * embed[e];
+        return;
+    }
     float s = 0.f;
     if (e < E) {
         const float* w = W + c0 + e;
@@ -74,6 +84,23 @@ __global__ __launch_bounds__(1024) void state_embed_grad_kernel(const float* __r
         for (int k = 0; k < 16; ++k) t += part[k][e];
         g_embed[e] += t;
     }
+}
+
+// out[j][n] = b[j][n] + sum_e W[j][n][c0[j] + e] embed[e]: the state embedding is the same 64 numbers in every row of a call, so
+// its product with the embedding columns of a layer's weight is a bias (M:295-296 concatenates it to every sample's encoding).
+// One wave per output, lane e holds one product, summed by a butterfly over the lanes: the order is fixed by the lane numbers.
+// Products and sum are formed in double and rounded to fp32 once, so b' is the correctly rounded value of b + W . embed (why not
+// fp32: DESIGN 2).  64 products per output: the launch is latency, not arithmetic.
+constexpr int FOLD_JOBS = 4;
+struct FoldTable { const float* W[FOLD_JOBS]; const float* b[FOLD_JOBS]; float* out[FOLD_JOBS]; int ldw[FOLD_JOBS]; int c0[FOLD_JOBS]; };
+__global__ __launch_bounds__(256) void embed_bias_fold_kernel(const FoldTable t, const float* __restrict__ embed, int N, int E) {
+    const int j = blockIdx.y, lane = threadIdx.x & 63;
+    const int n = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;                 // whole waves: n is wave-uniform
+    double p = lane < E ? (double)t.W[j][(size_t)n * t.ldw[j] + t.c0[j] + lane] * (double)embed[lane] : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+    if (lane == 0) t.out[j][n] = (float)((t.b[j] != nullptr ? (double)t.b[j][n] : 0.0) + p);
 }
 
 }  // namespace
@@ -123,7 +150,35 @@ extern "C" int hos_any_abs_below(const float* x, long long n, float thr, int32_t
 extern "C" int hos_state_embed_grad(const float* db, const float* W, int ldw, int c0, int N, int E, float* gb, float* g_embed, hos_stream_t stream) {
     if (!db || !W || !g_embed || N <= 0 || E <= 0 || c0 < 0) return HOS_E_ARG;
     if (E > 64) return HOS_E_SHAPE;
-    hipLaunchKernelGGL(state_embed_grad_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), db, W, ldw, c0, N, E, gb, g_embed);
+    hipLaunchKernelGGL(state_embed_grad_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), db, W, ldw, c0, N, E, gb, g_embed,
+                       (const float*)nullptr, (float*)nullptr, 0);
+    return hos_launch_status();
+}
+
+// The same launch for a layer that took the embedding as a bias: additionally dW [N, lddw][:, c0 : c0 + E] += db (x) embed, the
+// weight gradient of the embedding columns, which no GEMM of that layer formed.
+extern "C" int hos_state_embed_grad_w(const float* db, const float* W, int ldw, int c0, int N, int E, float* gb, float* g_embed,
+                                      const float* embed, float* dW, int lddw, hos_stream_t stream) {
+    if (!db || !W || !g_embed || !embed || !dW || N <= 0 || E <= 0 || c0 < 0) return HOS_E_ARG;
+    if (E > 64 || lddw < c0 + E || ldw < c0 + E) return HOS_E_SHAPE;
+    hipLaunchKernelGGL(state_embed_grad_kernel, dim3(1 + hos_cdiv(N, 16)), dim3(1024), 0, static_cast<hipStream_t>(stream), db, W, ldw, c0, N,
+                       E, gb, g_embed, embed, dW, lddw);
+    return hos_launch_status();
+}
+
+// out[j] [N] = b[j] [N] (NULL: 0) + W[j] [N, ldw[j]][:, c0[j] : c0[j] + E] . embed [E], for 1 <= n <= 4 layers in one launch
+// (host arrays, read during the call): the per-call biases of an MLP whose rows carry no embedding columns.  E <= 64.
+extern "C" int hos_embed_bias_fold(int n, const float* const* W, const int* ldw, const int* c0, const float* const* b, float* const* out,
+                                   const float* embed, int N, int E, hos_stream_t stream) {
+    if (n <= 0 || n > FOLD_JOBS || !W || !ldw || !c0 || !b || !out || !embed || N <= 0 || E <= 0) return HOS_E_ARG;
+    if (E > 64) return HOS_E_SHAPE;
+    FoldTable t{};
+    for (int j = 0; j < n; ++j) {
+        if (!W[j] || !out[j] || c0[j] < 0) return HOS_E_ARG;
+        if (ldw[j] < c0[j] + E) return HOS_E_SHAPE;
+        t.W[j] = W[j]; t.b[j] = b[j]; t.out[j] = out[j]; t.ldw[j] = ldw[j]; t.c0[j] = c0[j];
+    }
+    hipLaunchKernelGGL(embed_bias_fold_kernel, dim3(hos_cdiv(N, 4), n), dim3(256), 0, static_cast<hipStream_t>(stream), t, embed, N, E);
     return hos_launch_status();
 }
 

@@ -39,7 +39,7 @@ except Exception:  # gin is absent in the build image
 
 POS_FEATS = 504          # 2 * 12 levels * 21 directions
 EMBED = 64
-X_LD = 576               # 568 padded to a multiple of 32
+X_LD = 512               # the MLP's row operand: [IPE 504 | 0 x 8]; the state embedding enters as a bias (`_fold_biases`)
 VIEW_FEATS = 27
 XV_LD = 288              # 256 bottleneck + 27 view features, padded to a multiple of 32
 
@@ -139,7 +139,7 @@ class MipNeRF360MLP(FlatModule):
                 fan = netwidth
         if (netdepth - 1) % skip_layer == 0 and netdepth - 1 > 0:
             raise NotImplementedError("skip concat feeding the heads is not used by any shipped config")
-        # skip consumers see [h | x] with x padded to X_LD
+        # skip consumers see [h | x]; their weight keeps the reference's [netwidth | 504 + 64] columns (padded to 32)
         for i in self._skip_consumers:
             if i < netdepth:
                 L = self._layers[i]
@@ -210,10 +210,24 @@ class MipNeRF360MLP(FlatModule):
         flat = self.store.grad if grad else self.store.param
         return L.W.view(flat), L.b.view(flat).view(-1)
 
-    def _forward_impl(self, X: torch.Tensor, viewdirs: Optional[torch.Tensor], B: int, S: int, save: bool):
-        """X [P, X_LD] encoded samples -> density [P], rgb [P,3] | None, saved activations."""
+    def _fold_biases(self, state: int) -> Dict[int, torch.Tensor]:
+        """{layer: b + W[:, embedding columns] @ embed[state]} for layer 0 and every skip consumer, one launch per MLP call.  The
+        reference concatenates the state embedding to every sample's encoding (M:295-296): the same 64 numbers in every row, so
+        their product with a layer's weight is a bias, and the rows the GEMMs read are X_LD = 512 columns instead of 576.  The
+        weights keep their layout: a GEMM over 512 columns meets the first 8 embedding weights against the zero padding of X."""
+        W = self.netwidth
+        idx = [0] + sorted(i for i in self._skip_consumers if i < len(self._layers))
+        Wb = [self._w(self._layers[i]) for i in idx]
+        outs = ops.embed_bias_fold([w for w, _ in Wb], [POS_FEATS if i == 0 else W + POS_FEATS for i in idx], [b for _, b in Wb],
+                                   self._embeds.view(self.store.param)[state], W)
+        return dict(zip(idx, outs))
+
+    def _forward_impl(self, X: torch.Tensor, viewdirs: Optional[torch.Tensor], B: int, S: int, save: bool, state: int):
+        """X [P, X_LD] encoded samples (no embedding columns) of object state `state` -> density [P], rgb [P,3] | None, saved
+        activations."""
         if isinstance(X, tuple) or self._use_planes():
-            return self._forward_planes(X, viewdirs, B, S, save)
+            return self._forward_planes(X, viewdirs, B, S, save, state)
+        folded = self._fold_biases(state)
         P = X.shape[0]
         dev = X.device
         W = self.netwidth
@@ -228,10 +242,11 @@ class MipNeRF360MLP(FlatModule):
                     ping[i & 1] = torch.empty(P, W, device=dev)
                 out = ping[i & 1]
             Wt, bt = self._w(L)
+            bt = folded.get(i, bt)
             if i in self._skip_consumers:
                 ops.linear_fwd(h, W, Wt, bt, W, out, ops.EPI_RELU, A1=X, K1=X_LD)
             else:
-                ops.linear_fwd(h, L.Kpad, Wt, bt, W, out, ops.EPI_RELU)
+                ops.linear_fwd(h, X_LD if i == 0 else L.Kpad, Wt, bt, W, out, ops.EPI_RELU)
             if save:
                 acts.append(out)
             h = out
@@ -295,7 +310,7 @@ class MipNeRF360MLP(FlatModule):
         dz = torch.empty(P, W, device=dev)
         ops.linear_dgrad(dyh, Wt, Hs.Npad, W, dz, mask_src=h_last)
         # trunk, last layer first
-        embed_cols = []   # (temporary bias-grad, weight region, first embedding column)
+        embed_cols = []   # (temporary bias-grad, weight region, first embedding column, bias gradient, weight gradient)
         tmps = ops.zeros_many([(self._layers[0].Npad,)] * (1 + len(self._skip_consumers)), dev)      # one launch for the bias-gradient temporaries
         for i in range(len(self._layers) - 1, -1, -1):
             L = self._layers[i]
@@ -306,11 +321,11 @@ class MipNeRF360MLP(FlatModule):
                 tmp = tmps.pop()
                 ops.linear_wgrad(dz, inp, gW, tmp, W, W)
                 ops.linear_wgrad(dz, X, gW, None, W, X_LD, w_col0=W)
-                embed_cols.append((tmp, Wt, W + POS_FEATS, gb))
+                embed_cols.append((tmp, Wt, W + POS_FEATS, gb, gW))
             elif i == 0:
                 tmp = tmps.pop()
                 ops.linear_wgrad(dz, X, gW, tmp, W, X_LD)
-                embed_cols.append((tmp, Wt, POS_FEATS, gb))
+                embed_cols.append((tmp, Wt, POS_FEATS, gb, gW))
             else:
                 ops.linear_wgrad(dz, inp, gW, gb, W, W)
             if i > 0:
@@ -318,10 +333,12 @@ class MipNeRF360MLP(FlatModule):
                 ops.linear_dgrad(dz, Wt, W, W, dz_prev, mask_src=inp)
                 dz = dz_prev
         # state-embedding gradient: the 64 embedding columns of x are constant over samples, so
-        # d embed = (sum_p dZ[p,:]) @ W[:, embed cols] = db @ W[:, embed cols]   (M:295-296)
+        # d embed = (sum_p dZ[p,:]) @ W[:, embed cols] = db @ W[:, embed cols]   (M:295-296), and the weight gradient of those
+        # columns is db (x) embed (the wgrad launches above saw X without them)
         g_embed = self._embeds.view(self.store.grad)[state]
-        for tmp, Wt, c0, gb in embed_cols:       # gb += db and g_embed += db @ W[:, embed columns], one launch per layer
-            ops.state_embed_grad(tmp, Wt, c0, W, gb, g_embed)
+        embed = self._embeds.view(self.store.param)[state]
+        for tmp, Wt, c0, gb, gW in embed_cols:   # gb += db, g_embed += db @ W[:, embed columns], dW[:, embed columns] += db (x) embed: one launch per layer
+            ops.state_embed_grad_w(tmp, Wt, c0, W, gb, g_embed, embed, gW)
 
     # ------------------------------------------------------------------ planes path (ops.GEMM_PLANES)
     PLANES_MIN_WIDTH = 256
@@ -363,9 +380,10 @@ class MipNeRF360MLP(FlatModule):
             WT = ops.split_planes_T_batch([L.W.view(st.param) for L in specs])        # one launch for the whole MLP
         return W16, WT
 
-    def _forward_planes(self, X, viewdirs, B: int, S: int, save: bool):
+    def _forward_planes(self, X, viewdirs, B: int, S: int, save: bool, state: int):
         """X: (fp16 Planes, bf16 Planes | None) from hos_encode_ipe_planes, or an fp32 [P, X_LD] tensor (split here)."""
         W = self.netwidth
+        folded = self._fold_biases(state)
         W16, WT = self._weight_planes(need_t=save)
         one_fmt = self._bf16_fwd()
         if isinstance(X, tuple):
@@ -392,7 +410,7 @@ class MipNeRF360MLP(FlatModule):
                 if ping[i & 1] is None:
                     ping[i & 1] = ops.Planes.empty(P, W, fdt, dev)
                 out, outb = ping[i & 1], (ping[i & 1] if one_fmt else None)
-            _, bt = self._w(L)
+            bt = folded[i] if i in folded else self._w(L)[1]
             Yf, Ybf = (None, out) if one_fmt else (out, outb)
             if i in self._skip_consumers:
                 ops.linearp_fwd(h, W, W16[i], bt, P, W, True, Yf, Ybf, A1=X16, K1=X_LD)
@@ -473,11 +491,11 @@ class MipNeRF360MLP(FlatModule):
                 tmp = tmps.pop()
                 ops.linearp_wgrad(dz, inp_b, gW, tmp, P, W, W)
                 ops.linearp_wgrad(dz, sv.Xb, gW, None, P, W, X_LD, w_col0=W)
-                embed_cols.append((tmp, Wt, W + POS_FEATS, gb))
+                embed_cols.append((tmp, Wt, W + POS_FEATS, gb, gW))
             elif i == 0:
                 tmp = tmps.pop()
                 ops.linearp_wgrad(dz, sv.Xb, gW, tmp, P, W, X_LD)
-                embed_cols.append((tmp, Wt, POS_FEATS, gb))
+                embed_cols.append((tmp, Wt, POS_FEATS, gb, gW))
             else:
                 ops.linearp_wgrad(dz, inp_b, gW, gb, P, W, W)
             if i > 0:
@@ -485,8 +503,9 @@ class MipNeRF360MLP(FlatModule):
                 ops.linearp_dgrad(dz, sv.WT[i], W, P, W, mask=sv.y16[i - 1], dX=dz_prev)
                 dz = dz_prev
         g_embed = self._embeds.view(self.store.grad)[state]
-        for tmp, Wt, c0, gb in embed_cols:       # gb += db and g_embed += db @ W[:, embed columns], one launch per layer
-            ops.state_embed_grad(tmp, Wt, c0, W, gb, g_embed)
+        embed = self._embeds.view(self.store.param)[state]
+        for tmp, Wt, c0, gb, gW in embed_cols:   # gb += db, g_embed += db @ W[:, embed columns], dW[:, embed columns] += db (x) embed: one launch per layer
+            ops.state_embed_grad_w(tmp, Wt, c0, W, gb, g_embed, embed, gW)
 
     # ------------------------------------------------------------------ reference-style forward
     def forward(self, gaussians, viewdirs, randomized, is_train, time):
@@ -507,17 +526,17 @@ class MipNeRF360MLP(FlatModule):
     def query(self, tdist, rays_o, rays_d, radii, viewdirs, time: float) -> Dict[str, torch.Tensor]:
         B, S = tdist.shape[0], tdist.shape[1] - 1
         state = select_state(time, self.transitions_times)
-        embed = self._embeds.view(self.store.param)[state]
+        # rows without the embedding columns (embed = None): [IPE 504 | 0 x 8]
         if self._use_planes():      # the encoder writes the 16-bit planes the trunk consumes (no fp32 copy of X)
             one_fmt = self._bf16_fwd()
-            X = ops.encode_ipe_planes(tdist, rays_o, rays_d, radii, self.pos_basis_t, embed, X_LD,
+            X = ops.encode_ipe_planes(tdist, rays_o, rays_d, radii, self.pos_basis_t, None, X_LD,
                                       want_bf16=torch.is_grad_enabled() or one_fmt, want_fp16=not one_fmt)
         else:
-            X = ops.encode_ipe(tdist, rays_o, rays_d, radii, self.pos_basis_t, embed, X_LD)
+            X = ops.encode_ipe(tdist, rays_o, rays_d, radii, self.pos_basis_t, None, X_LD)
         if torch.is_grad_enabled():
             density, rgb = _MLPFn.apply(self._token, self, X, viewdirs, B, S, state)
         else:
-            density, rgb, _ = self._forward_impl(X, viewdirs, B, S, save=False)
+            density, rgb, _ = self._forward_impl(X, viewdirs, B, S, save=False, state=state)
         density = density.view(B, S)
         rgb = self._zero_rgb(B, S, density.device) if self.disable_rgb else rgb.view(B, S, 3)
         return {"density": density, "rgb": rgb}
@@ -533,14 +552,13 @@ class MipNeRF360MLP(FlatModule):
         if viewdirs.shape != pts.shape:
             raise ValueError(f"query_points: viewdirs {tuple(viewdirs.shape)} must be one direction per point, {tuple(pts.shape)}")
         state = select_state(time, self.transitions_times)
-        embed = self._embeds.view(self.store.param)[state]
         pts = pts.contiguous()
         if self._use_planes():
             one_fmt = self._bf16_fwd()
-            X = ops.encode_ipe_points_planes(pts, var, self.pos_basis_t, embed, X_LD, want_bf16=one_fmt, want_fp16=not one_fmt)
+            X = ops.encode_ipe_points_planes(pts, var, self.pos_basis_t, None, X_LD, want_bf16=one_fmt, want_fp16=not one_fmt)
         else:
-            X = ops.encode_ipe_points(pts, var, self.pos_basis_t, embed, X_LD)
-        density, rgb, _ = self._forward_impl(X, viewdirs.contiguous(), P, 1, save=False)
+            X = ops.encode_ipe_points(pts, var, self.pos_basis_t, None, X_LD)
+        density, rgb, _ = self._forward_impl(X, viewdirs.contiguous(), P, 1, save=False, state=state)
         return {"density": density, "rgb": self._zero_rgb(P, 1, density.device).view(P, 3) if self.disable_rgb else rgb}
 
 
@@ -550,7 +568,7 @@ class _MLPFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, token, mlp: MipNeRF360MLP, X, viewdirs, B, S, state):
-        density, rgb, saved = mlp._forward_impl(X, viewdirs, B, S, save=True)
+        density, rgb, saved = mlp._forward_impl(X, viewdirs, B, S, save=True, state=state)
         ctx.mlp, ctx.saved, ctx.state = mlp, saved, state
         ctx.mode = ops.get_gemm_mode()           # the backward pass (another host thread) runs in the arithmetic of this forward
         ctx.density, ctx.rgb = density, rgb

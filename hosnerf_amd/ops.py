@@ -1188,6 +1188,29 @@ def state_embed_grad(db, W, c0, N, gb, g_embed):
     call("hos_state_embed_grad", ptr(db), ptr(W), W.stride(0), c0, N, g_embed.numel(), ptr(gb), ptr(g_embed))
 
 
+def state_embed_grad_w(db, W, c0, N, gb, g_embed, embed, dW):
+    """`state_embed_grad` for a layer that took the embedding as a bias (`embed_bias_fold`): the same launch also writes the weight
+    gradient of the embedding columns, dW[:N, c0:c0+len(embed)] += db[:N] (x) embed."""
+    call("hos_state_embed_grad_w", ptr(db), ptr(W), W.stride(0), c0, N, g_embed.numel(), ptr(gb), ptr(g_embed), ptr(embed), ptr(dW),
+         dW.stride(0))
+
+
+def embed_bias_fold(Ws, c0s, bs, embed, N: int):
+    """[b + W[:N, c0:c0+len(embed)] @ embed for (W, c0, b) in zip(Ws, c0s, bs)] -- 4 layers of one MLP per launch (more layers: more
+    launches), summed in double in a fixed order and rounded once: the state embedding of a call as the bias of the layers that
+    read it (hos_embed_bias_fold)."""
+    import ctypes
+    n = len(Ws)
+    c0s = list(c0s)
+    outs = list(torch.empty(n, N, device=embed.device).unbind(0))
+    for s in range(0, n, 4):
+        e = min(n, s + 4)
+        call("hos_embed_bias_fold", e - s, _table([ptr(w) for w in Ws[s:e]]), _table([w.stride(0) for w in Ws[s:e]], ctypes.c_int),
+             _table(c0s[s:e], ctypes.c_int), _table([ptr(b) for b in bs[s:e]]), _table([ptr(o) for o in outs[s:e]]), ptr(embed), N,
+             embed.numel())
+    return outs
+
+
 def head_grad(g_density, density, g_rgb, rgb, rgb_padding, dz_density, col_dd, dz_rgb):
     P = density.numel()
     call("hos_head_grad", ptr(g_density), ptr(density), ptr(g_rgb), ptr(rgb), P, float(rgb_padding),

@@ -379,7 +379,10 @@ int hos_resample(const float* sdist_prev, const float* w_prev, int n_prev, int B
 /* Conical-frustum cast + contraction + lift + integrated positional encoding (+ state embedding
  * columns + zero pad): replaces H:279-339, H:33-68 (closed-form Jacobian), H:71-89, M:295-296.
  *   X [B*S, ldx]: cols [0,504) IPE (level-major, 21 dirs; sin part then sin(.+pi/2) part),
- *                 [504,568) = state embedding, [568,ldx) = 0.   basis [3,21] row-major. */
+ *                 [504,568) = state embedding, [568,ldx) = 0.   basis [3,21] row-major.
+ *   embed = NULL (all four encoder entry points): the row form without the embedding, [0,504) IPE, [504,ldx) = 0, ldx >= 504
+ *   (planes: ld >= 512) -- for an MLP that takes the embedding as a bias (hos_embed_bias_fold).  Columns [0,504) are the same bits
+ *   in both forms. */
 int hos_encode_ipe(const float* tdist, const float* rays_o, const float* rays_d, const float* radii,
                    const float* basis, const float* embed, int B, int S, float* X, int ldx,
                    hos_stream_t stream);
@@ -801,6 +804,17 @@ int hos_any_abs_below(const float* x, long long n, float thr, int32_t* flag, hos
 /* gb [N] += db (NULL: skip); g_embed [E <= 64] += db [N] . W [N, ldw][:, c0 : c0 + E]: gradient of the per-call state embedding
  * through the first / skip layer of a MipNeRF360MLP (M:295-296). */
 int hos_state_embed_grad(const float* db, const float* W, int ldw, int c0, int N, int E, float* gb, float* g_embed, hos_stream_t stream);
+/* The same launch for a layer that took the embedding as a bias (hos_embed_bias_fold): additionally
+ * dW [N, lddw][:, c0 : c0 + E] += db (x) embed, the weight gradient of the embedding columns (every element by one thread, no atomics).
+ * HOS_E_SHAPE: E > 64, or ldw / lddw < c0 + E. */
+int hos_state_embed_grad_w(const float* db, const float* W, int ldw, int c0, int N, int E, float* gb, float* g_embed,
+                           const float* embed, float* dW, int lddw, hos_stream_t stream);
+/* out[j] [N] = b[j] [N] (NULL: 0) + W[j] [N, ldw[j]][:, c0[j] : c0[j] + E] . embed [E] for n <= 4 layers in one launch: the state
+ * embedding of a MipNeRF360MLP call as a bias of its first / skip layer (M:295-296 concatenates the same E numbers to every row).
+ * Products and sum in double in a fixed order (one wave per output), rounded to fp32 once.  The arrays are host arrays, read during
+ * the call.  E <= 64. */
+int hos_embed_bias_fold(int n, const float* const* W, const int* ldw, const int* c0, const float* const* b, float* const* out,
+                        const float* embed, int N, int E, hos_stream_t stream);
 /* hos_embed_bwd added to a residual cotangent: g_x [P, 3] = res + d(features)/dx (rows past *rows_dev: res alone); g_x may be
  * uninitialised (mlp_offset.py:66-70, xyz = x + offset). */
 int hos_embed_bwd_res(const float* x, const float* band_w, int num_freqs, int identity, const float* dA, int lda, int colA,

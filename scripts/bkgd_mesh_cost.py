@@ -61,7 +61,7 @@ def main():
     Nx, Ny, Nz = dims
     N = Nx * Ny * Nz
     firsts = list(range(0, N, args.chunk))
-    embed = mlp._embeds.view(mlp.store.param)[field["state"]]
+    embed = None            # the MLP's row form: no embedding columns, the state embedding enters as a bias
     planes = mlp._use_planes()
     one_fmt = mlp._bf16_fwd()
     alpha = torch.empty_like(field["alpha"])
@@ -82,7 +82,7 @@ def main():
                 vd = view.expand(rows, 3).contiguous()
                 part = {}
                 X = timed(part, "e", lambda: encode(pts))
-                dens = timed(part, "m", lambda: mlp._forward_impl(X, vd, rows, 1, save=False)[0])
+                dens = timed(part, "m", lambda: mlp._forward_impl(X, vd, rows, 1, save=False, state=field["state"])[0])
                 timed(part, "a", lambda: ops.grid_alpha_density(dens, h, dims, first, alpha))
                 enc, mlp_ms, alpha_ms = enc + part["e"][0], mlp_ms + part["m"][0], alpha_ms + part["a"][0]
                 del X, dens

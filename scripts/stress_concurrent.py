@@ -6,7 +6,7 @@ import json, os, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hosnerf_amd import ops, synth
-from hosnerf_amd.mipnerf360 import MipNeRF360
+from hosnerf_amd.mipnerf360 import X_LD, MipNeRF360
 from hosnerf_amd.human_nerf import Network, default_cfg
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
@@ -22,13 +22,12 @@ b = {k: v.to(dev) for k, v in synth.stage1_batch(B, seed=777).items()}
 mlp = model.mlps[int(os.environ.get("LEVEL", "0"))]
 S = 64 if mlp.disable_rgb else 32
 tdist = torch.linspace(0.2, 5.0, S + 1, device=dev).expand(B, S + 1).contiguous()
-embed = mlp._embeds.view(mlp.store.param)[1]
 SAVE = os.environ.get("SAVE", "1") == "1"
 
 
 def query():
-    X = ops.encode_ipe_planes(tdist, b["rays_o"], b["rays_d"], b["radii"], mlp.pos_basis_t, embed, 576, want_bf16=SAVE)
-    density, rgb, saved = mlp._forward_planes(X, b["viewdirs"], B, S, save=SAVE)
+    X = ops.encode_ipe_planes(tdist, b["rays_o"], b["rays_d"], b["radii"], mlp.pos_basis_t, None, X_LD, want_bf16=SAVE)
+    density, rgb, saved = mlp._forward_planes(X, b["viewdirs"], B, S, save=SAVE, state=1)
     outs = {"X16": X[0].t, "density": density}
     if rgb is not None:
         outs["rgb"] = rgb
