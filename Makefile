@@ -21,7 +21,7 @@ all: $(LIB) $(if $(HAVE_RCCL),$(COMM),comm-skipped)
 comm-skipped:
 	@echo "note: rccl.h / librccl.so not found under $(ROCM_PATH): libhoscomm.so not built (hosnerf_amd.comm falls back to torch.distributed)"
 
-build/%.o: hosnerf_amd/csrc/%.hip hosnerf_amd/csrc/hos_common.h hosnerf_amd/csrc/hos_gemm_common.h include/hosrender.h
+build/%.o: hosnerf_amd/csrc/%.hip $(wildcard hosnerf_amd/csrc/*.h) include/hosrender.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 

@@ -22,7 +22,7 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef Vec<_Float16>::x8 h8;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 constexpr int CT = 256;             // threads per workgroup = 4 waves, one per SIMD
@@ -61,33 +61,14 @@ constexpr int AUX_FLOATS = NL * CW + 3 * CW + 4;
 constexpr int AUX_BYTES = (AUX_FLOATS * 4 + 15) & ~15;
 constexpr int SMEM_BYTES = 2 * CBUF + AUX_BYTES;
 
-__device__ __forceinline__ void dma16(const void* gsrc, void* ldst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)ldst, 16, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 mfma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-    return acc;
-}
-
-__device__ __forceinline__ void split_to(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);        // one v_med3 (fminf(fmaxf()) adds a canonicalising v_max)
-    lo = (_Float16)(x - (float)hi);
-}
-
 // eight fp32 values at p[0..3] and p[8..11] (the k-slots of this half-lane inside a group of 16) -> (hi, lo) fragments
 __device__ __forceinline__ void load_split8(const float* p, h8& hi, h8& lo) {
     const float4 a = *reinterpret_cast<const float4*>(p);
     const float4 b = *reinterpret_cast<const float4*>(p + 8);
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
-    for (int c = 0; c < 8; ++c) { _Float16 h, l; split_to(v[c], h, l); hi[c] = h; lo[c] = l; }
+    for (int c = 0; c < 8; ++c) { _Float16 h, l; split1<_Float16>(v[c], h, l); hi[c] = h; lo[c] = l; }
 }
-
-#define CH_RD128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
 
 template <bool FOLD>
 __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
@@ -194,49 +175,49 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
                 // are a second straight-line group inside ONE branch.
                 if (FOLD && l == 0) {
                     // folded first layer: the four k-steps of the hann features (operand slots 8..11), same discipline
-                    CH_RD128(fh[0], la, 0);
-                    CH_RD128(fl[0], la, 1024);
+                    HOS_RD128(fh[0], la, 0);
+                    HOS_RD128(fl[0], la, 1024);
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         if (s < 3) {
-                            CH_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
-                            CH_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
+                            HOS_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
+                            HOS_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
                             asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fh[s & 1]), "+v"(fl[s & 1]));
                         } else {
                             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fh[0]), "+v"(fl[0]), "+v"(fh[1]), "+v"(fl[1]));
                         }
-                        acc[ob] = mfma3(fh[s & 1], fl[s & 1], bh[8 + s], bl[8 + s], acc[ob]);
+                        acc[ob] = mma3<_Float16>(fh[s & 1], fl[s & 1], bh[8 + s], bl[8 + s], acc[ob]);
                         if ((s & 1) == 0) issue_round(nl, nob, npar, s >> 1);
                     }
                     if (nrounds == 4) { issue_round(nl, nob, npar, 2); issue_round(nl, nob, npar, 3); }     // (0, 3) -> layer 1
                 } else {
-                CH_RD128(fh[0], la, 0);
-                CH_RD128(fl[0], la, 1024);
+                HOS_RD128(fh[0], la, 0);
+                HOS_RD128(fl[0], la, 1024);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     if (s < 7) {
-                        CH_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
-                        CH_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
+                        HOS_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
+                        HOS_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
                         asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fh[s & 1]), "+v"(fl[s & 1]));
                     } else {
                         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fh[0]), "+v"(fl[0]), "+v"(fh[1]), "+v"(fl[1]));
                     }
-                    acc[ob] = mfma3(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
+                    acc[ob] = mma3<_Float16>(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
                     if ((s & 1) == 0 && (s >> 1) < nrounds) issue_round(nl, nob, npar, s >> 1);
                 }
                 if (ks == 12) {
-                    CH_RD128(fh[0], la, 16 * 1024);
-                    CH_RD128(fl[0], la, 17 * 1024);
+                    HOS_RD128(fh[0], la, 16 * 1024);
+                    HOS_RD128(fl[0], la, 17 * 1024);
 #pragma unroll
                     for (int s = 8; s < 12; ++s) {
                         if (s < 11) {
-                            CH_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
-                            CH_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
+                            HOS_RD128(fh[(s + 1) & 1], la, (2 * s + 2) * 1024);
+                            HOS_RD128(fl[(s + 1) & 1], la, (2 * s + 3) * 1024);
                             asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fh[s & 1]), "+v"(fl[s & 1]));
                         } else {
                             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fh[0]), "+v"(fl[0]), "+v"(fh[1]), "+v"(fl[1]));
                         }
-                        acc[ob] = mfma3(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
+                        acc[ob] = mma3<_Float16>(fh[s & 1], fl[s & 1], bh[s], bl[s], acc[ob]);
                         if ((s & 1) == 0 && (s >> 1) < nrounds) issue_round(nl, nob, npar, s >> 1);
                     }
                 }
@@ -281,7 +262,7 @@ __global__ __launch_bounds__(CT, 2) void chain128_kernel(ChainArgs a) {
                     big |= mx > HOS_RANGE_LIMIT;
                     h8 hi, lo;
 #pragma unroll
-                    for (int c = 0; c < 8; ++c) { _Float16 h_, l_; split_to(v[c], h_, l_); hi[c] = h_; lo[c] = l_; }
+                    for (int c = 0; c < 8; ++c) { _Float16 h_, l_; split1<_Float16>(v[c], h_, l_); hi[c] = h_; lo[c] = l_; }
                     bh[2 * ob + tq] = hi;
                     bl[2 * ob + tq] = lo;
                 }
@@ -346,7 +327,7 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(PackArgs p) {
         if (FOLD && l == 0) w = k < p.nfeat ? p.W[0][(size_t)n * p.ldw[0] + p.ncond + k] : 0.f;
         else w = p.W[l][(size_t)n * p.ldw[l] + k];
         _Float16 hi, lo;
-        split_to(w, hi, lo);
+        split1<_Float16>(w, hi, lo);
         const size_t o = (((size_t)(ob * ks + s) * 2) * 64 + lane) * 8 + c;
         dst[o] = __builtin_bit_cast(uint16_t, hi);
         dst[o + 64 * 8] = __builtin_bit_cast(uint16_t, lo);

@@ -16,6 +16,7 @@
 // reference does (for 2^11*x ~ 4096 the fp32 ulp is 4.9e-4 -- a fused or cosf() variant differs
 // from the reference by up to 2.4e-4, more than the whole parity budget).
 #include "hos_common.h"
+#include "hos_mfma.h"
 
 namespace {
 
@@ -56,15 +57,8 @@ __device__ __forceinline__ float enc_exp(float x) {
     return __builtin_amdgcn_exp2f(t) * __builtin_fmaf(e, 0.69314718f, 1.0f);
 }
 
-// (hi, lo) split of one value for the interleaved-planes layout of hos_gemmp.hip: fp16 hi saturates at +-65504
-template <typename E> __device__ __forceinline__ float hi_clamp(float x) { return x; }
-template <> __device__ __forceinline__ float hi_clamp<_Float16>(float x) { return __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
-template <typename E> __device__ __forceinline__ void split_store(unsigned short* __restrict__ P, size_t o, float x) {
-    const E h = (E)hi_clamp<E>(x);
-    const E l = (E)(x - (float)h);
-    P[o] = __builtin_bit_cast(unsigned short, h);
-    P[o + 32] = __builtin_bit_cast(unsigned short, l);
-}
+// The (hi, lo) split of hos_mfma.h for the interleaved-planes layout of hos_gemmp.hip (both hi parts, then both lo parts: as two
+// split1 calls the kernel comes out with another schedule), two values per call:
 // two adjacent columns (c even) of one row: the (hi, hi) and (lo, lo) pairs as one 4-byte store each -- half the store
 // instructions of the per-column form (the stores were a quarter of this kernel's time).
 // Round 5, measured and dropped (profiles/r05_ab_encoder_output_stage.txt): staging 16 samples' rows as fp32 in LDS and writing
@@ -72,12 +66,11 @@ template <typename E> __device__ __forceinline__ void split_store(unsigned short
 // formats, 277 vs 220 us with one -- the kernel is bound by its 756 sinf / expf evaluations per sample (one format: 2.7 TB/s of
 // stores, two formats: 3.5), not by store issue, and the staging's barriers + 48 KB of LDS per workgroup cost occupancy.
 template <typename E> __device__ __forceinline__ void split_store2(unsigned short* __restrict__ P, size_t o, float x0, float x1) {
-    const E h0 = (E)hi_clamp<E>(x0), h1 = (E)hi_clamp<E>(x1);
+    const E h0 = (E)hi_src<E>(x0), h1 = (E)hi_src<E>(x1);
     const E l0 = (E)(x0 - (float)h0), l1 = (E)(x1 - (float)h1);
     *reinterpret_cast<uint32_t*>(P + o) = (uint32_t)__builtin_bit_cast(unsigned short, h0) | ((uint32_t)__builtin_bit_cast(unsigned short, h1) << 16);
-    *reinterpret_cast<uint32_t*>(P + o + 32) = (uint32_t)__builtin_bit_cast(unsigned short, l0) | ((uint32_t)__builtin_bit_cast(unsigned short, l1) << 16);
+    *reinterpret_cast<uint32_t*>(P + o + PL_LO) = (uint32_t)__builtin_bit_cast(unsigned short, l0) | ((uint32_t)__builtin_bit_cast(unsigned short, l1) << 16);
 }
-__device__ __forceinline__ size_t plane_off(long row, int c, int ld) { return (size_t)row * (2 * ld) + (c >> 5) * 64 + (c & 31); }
 
 // H:37-42: the contraction z of x and its closed-form Jacobian J (the identity on r2 <= 1; r2 is clamped at 1e-32, so x = 0 takes that branch)
 __device__ __forceinline__ void contract_point(const float (&x)[3], float (&z)[3], float (&J)[3][3]) {
@@ -259,6 +252,7 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
             const int j0 = c % NDIR, j1 = (c + 1) % NDIR;
             const float sc0 = (float)(1 << (c / NDIR)), sc1 = (float)(1 << ((c + 1) / NDIR));
             const float sq0 = sc0 * sc0, sq1 = sc1 * sc1;
+            // the column terms of pl_off (written out: through a shared function the index arithmetic below comes out differently)
             const int co0 = (c >> 5) * 64 + (c & 31), co1 = ((c + HALF) >> 5) * 64 + ((c + HALF) & 31);
             const size_t pitch = (size_t)2 * ldx;
             const int n_s = (int)((P - p0) < (long)SB ? (P - p0) : (long)SB);
@@ -291,7 +285,7 @@ __global__ __launch_bounds__(256) void encode_ipe_kernel(
             const int s = it / (tail / 2), c = (it % (tail / 2)) * 2;
             if (p0 + s >= P) break;
             const float v0 = (c < NEMB) ? s_embed[c] : 0.f, v1 = (c + 1 < NEMB) ? s_embed[c + 1] : 0.f;
-            const size_t o = plane_off(p0 + s, NIPE + c, ldx);
+            const size_t o = pl_off(p0 + s, NIPE + c, ldx);
             if (p16 != nullptr) split_store2<_Float16>(p16, o, v0, v1);
             if (pb != nullptr) split_store2<__bf16>(pb, o, v0, v1);
         }

@@ -24,8 +24,6 @@ constexpr int BK = 32;
 constexpr int NT = 256;
 
 
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // ---- global -> register staging -------------------------------------------------------------
 // K-contiguous operand P[i][k]: tile rows i0.., 32 floats of k.  thread -> (k4 = t&7, i = t>>3 + 32r)
 template <int BMN>

@@ -23,18 +23,6 @@
 // inside the ~56 B/clk/CU the L2 delivers; a 128x128 tile would need 42 B/clk/CU and starve.
 #include "hos_gemm_common.h"
 
-// Split element type: __bf16 (8-bit exponent: safe for gradients of any magnitude, ~2^-17 relative error per
-// product) for DGRAD/WGRAD, _Float16 (11-bit mantissa: hi+lo carry 22 bits, ~2^-21 relative error -- fp32 grade)
-// for the FORWARD GEMMs whose operands (features, activations, weights) are O(1e-3..1e3) by construction.
-template <typename E> struct Vec { typedef E x8 __attribute__((ext_vector_type(8))); typedef E x4 __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ f32x16 mfma16(const Vec<__bf16>::x8& a, const Vec<__bf16>::x8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma16(const Vec<_Float16>::x8& a, const Vec<_Float16>::x8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 namespace {
 
 constexpr int BM = 256;
@@ -42,19 +30,6 @@ constexpr int BK = 32;
 constexpr int NT3 = 512;
 constexpr int ROWB = 64;          // bytes per LDS row per plane (32 bf16)
 constexpr int PF_DIST = 3;        // software L2 prefetch distance in K tiles (see `prefetch` in gemm3_kernel)
-
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-template <typename E> __device__ __forceinline__ float hi_src(float x) { return x; }
-// fp16 hi part saturates at +-65504 instead of overflowing to inf; the residual then lands in lo (exact up to 131008)
-template <> __device__ __forceinline__ float hi_src<_Float16>(float x) { return __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
-
-template <typename E>
-__device__ __forceinline__ void split4(const float4& v, typename Vec<E>::x4& hi, typename Vec<E>::x4& lo) {
-    hi[0] = (E)hi_src<E>(v.x); hi[1] = (E)hi_src<E>(v.y); hi[2] = (E)hi_src<E>(v.z); hi[3] = (E)hi_src<E>(v.w);
-    lo[0] = (E)(v.x - (float)hi[0]); lo[1] = (E)(v.y - (float)hi[1]);
-    lo[2] = (E)(v.z - (float)hi[2]); lo[3] = (E)(v.w - (float)hi[3]);
-}
 
 // byte offset of the 8-byte group holding k = kq*4 .. kq*4+3 of `row` inside one plane
 __device__ __forceinline__ int lds_off(int row, int kq) {
@@ -259,11 +234,7 @@ __global__ __launch_bounds__(NT3, 2) void gemm3_kernel(const GemmArgs a) {
 #pragma unroll
             for (int x = 0; x < TM; ++x)
 #pragma unroll
-                for (int y = 0; y < TN; ++y) {
-                    acc[x][y] = mfma16(al[x], bh[y], acc[x][y]);
-                    acc[x][y] = mfma16(ah[x], bl[y], acc[x][y]);
-                    acc[x][y] = mfma16(ah[x], bh[y], acc[x][y]);
-                }
+                for (int y = 0; y < TN; ++y) acc[x][y] = mma3<E>(ah[x], al[x], bh[y], bl[y], acc[x][y]);
         }
     };
 

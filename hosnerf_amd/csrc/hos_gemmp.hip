@@ -43,17 +43,6 @@ constexpr int PBK = 32;
 constexpr int PNT = 512;
 constexpr int PROWB = 64;
 
-template <typename E> struct PVec { typedef E x8 __attribute__((ext_vector_type(8))); typedef E x4 __attribute__((ext_vector_type(4))); };
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 pmfma(const PVec<__bf16>::x8& a, const PVec<__bf16>::x8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 pmfma(const PVec<_Float16>::x8& a, const PVec<_Float16>::x8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 enum PEpi { PEPI_F32 = 0, PEPI_PLANES_FWD = 1, PEPI_PLANES_DGRAD = 2, PEPI_WGRAD = 3 };
 
 struct PArgs {
@@ -75,14 +64,12 @@ struct PArgs {
 };
 
 template <typename E> __device__ __forceinline__ uint16_t to_bits(E v) { return __builtin_bit_cast(uint16_t, v); }
-template <typename E> __device__ __forceinline__ float clampE(float x) { return x; }
-template <> __device__ __forceinline__ float clampE<_Float16>(float x) { return __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
 
 // (hi, lo) of x packed as lo16 = hi bits, hi16 = lo bits
 template <typename E>
 __device__ __forceinline__ uint32_t split_pack(float x) {
-    const E h = (E)clampE<E>(x);
-    const E l = (E)(x - (float)h);
+    E h, l;
+    split1<E>(x, h, l);
     return (uint32_t)to_bits<E>(h) | ((uint32_t)to_bits<E>(l) << 16);
 }
 // the same dword for a value the epilogue holds in a register: the final pack is ONE packed conversion (lower half = the
@@ -90,7 +77,7 @@ __device__ __forceinline__ uint32_t split_pack(float x) {
 typedef float pf32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t split_pack_pk(float x, _Float16) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const float c = clampE<_Float16>(x);
+    const float c = hi_src<_Float16>(x);
     const pf32x2 v = {c, x - (float)(_Float16)c};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2));
 }
@@ -100,23 +87,15 @@ __device__ __forceinline__ uint32_t split_pack_pk(float x, __bf16) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2));
 }
 template <typename E>
-__device__ __forceinline__ void split1(float x, uint16_t& hi, uint16_t& lo) {
+__device__ __forceinline__ void split_bits(float x, uint16_t& hi, uint16_t& lo) {
     const uint32_t p = split_pack<E>(x);
     hi = (uint16_t)(p & 0xffffu); lo = (uint16_t)(p >> 16);
-}
-
-__device__ __forceinline__ void dma16(const void* gsrc, void* ldst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)ldst, 16, 0, 0);
-}
-__device__ __forceinline__ s16x4 lds_tr(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
 }
 
 // TR = false: both operands k-contiguous (FWD, DGRAD).  TR = true: both operands reduction-row-major (WGRAD).
 template <int BN, int EPI, typename EIN, bool TR>
 __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
-    typedef typename PVec<EIN>::x8 ex8;
+    typedef typename Vec<EIN>::x8 ex8;
     constexpr int WN = 2;
     constexpr int TM = PBM / (4 * 32);       // 2
     constexpr int TN = BN / (WN * 32);       // 4 or 2
@@ -245,7 +224,6 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
             for (int y = 0; y < TN; ++y) offB[y][hl] = lds_base + A_TILE + m_lane * B_PITCH + ((((wn * TN + y) * 2 + hl) ^ sw) << 6) + lcol;
         }
     }
-#define HOS_RD128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
 #define HOS_RDTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
     // fragment storage: k-contiguous form uses .v directly; TR form loads two 64-bit halves and joins them after the wait
     struct Frag { ex8 v; s16x4 h0, h1; };
@@ -344,9 +322,9 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
         __builtin_amdgcn_s_setprio(1);                                                                    \
         _Pragma("unroll") for (int i = 0; i < NM; ++i) {                                                  \
             HOS_ORDER_DECODE(i);                                                                          \
-            if (pr == 0)      acc[x][(YH) * TH + y] = pmfma(AL[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
-            else if (pr == 1) acc[x][(YH) * TH + y] = pmfma(AH[x].v, BL[y].v, acc[x][(YH) * TH + y]);     \
-            else              acc[x][(YH) * TH + y] = pmfma(AH[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
+            if (pr == 0)      acc[x][(YH) * TH + y] = mfma16(AL[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
+            else if (pr == 1) acc[x][(YH) * TH + y] = mfma16(AH[x].v, BL[y].v, acc[x][(YH) * TH + y]);     \
+            else              acc[x][(YH) * TH + y] = mfma16(AH[x].v, BH[y].v, acc[x][(YH) * TH + y]);     \
             __builtin_amdgcn_sched_barrier(0);                                                            \
             FILL(i);                                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                            \
@@ -621,7 +599,6 @@ __global__ __launch_bounds__(PNT, 2) void gemmp_kernel(const PArgs a) {
 #undef HOS_READ_A1
 #undef HOS_READ_B
 #undef HOS_READ_B1
-#undef HOS_RD128
 #undef HOS_RDTR
 }
 
@@ -654,9 +631,6 @@ int launchp(PArgs& a, int splits, hipStream_t stream) {
     return launchp_impl<BN, EPI, EIN, TR>(a, a.total, stream);
 }
 
-// element offset of (row r, column c) in an interleaved-planes array with `ld` logical columns: hi there, lo 32 further
-__device__ __forceinline__ size_t pl_off(int r, int c, int ld) { return (size_t)r * (2 * ld) + (c >> 5) * 64 + (c & 31); }
-
 // fp32 [R][lds] -> interleaved planes, row-major [R][ldo] (padding columns [C, ldo) zeroed) and/or transposed [C][ldt]
 template <typename E>
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ src, int lds, int R, int C,
@@ -672,10 +646,10 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
         tile[ty + 8 * k][tx] = v;
         if (out != nullptr && r < R && c < ldo) {
             uint16_t h, l;
-            split1<E>(v, h, l);
+            split_bits<E>(v, h, l);
             const size_t o = pl_off(r, c, ldo);
             out[o] = h;
-            out[o + 32] = l;
+            out[o + PL_LO] = l;
         }
     }
     if (outT == nullptr) return;
@@ -685,10 +659,10 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
         const int c = c0 + ty + 8 * k, r = r0 + tx;       // transposed: row index c, column r
         if (c < C && r < ldt) {
             uint16_t h, l;
-            split1<E>(r < R ? tile[tx][ty + 8 * k] : 0.f, h, l);
+            split_bits<E>(r < R ? tile[tx][ty + 8 * k] : 0.f, h, l);
             const size_t o = pl_off(c, r, ldt);
             outT[o] = h;
-            outT[o + 32] = l;
+            outT[o + PL_LO] = l;
         }
     }
 }
@@ -715,10 +689,10 @@ __global__ __launch_bounds__(256) void split_planes_T_batch_kernel(const SplitBa
         const int c = c0 + ty + 8 * k, r = r0 + tx;       // transposed: row index c, column r
         if (c < J.C && r < J.ldt) {
             uint16_t h, l;
-            split1<__bf16>(r < J.R ? tile[tx][ty + 8 * k] : 0.f, h, l);
+            split_bits<__bf16>(r < J.R ? tile[tx][ty + 8 * k] : 0.f, h, l);
             const size_t o = pl_off(c, r, J.ldt);
             J.outT[o] = h;
-            J.outT[o + 32] = l;
+            J.outT[o + PL_LO] = l;
         }
     }
 }
@@ -741,7 +715,7 @@ __global__ __launch_bounds__(256) void split_planes2_kernel(const float* __restr
             for (int k = 0; k < 4; ++k) p[k] = split_pack<_Float16>(v[k]);
             const size_t o = pl_off(r, c, ld16);
             *reinterpret_cast<uint2*>(p16 + o) = make_uint2((p[0] & 0xffffu) | (p[1] << 16), (p[2] & 0xffffu) | (p[3] << 16));
-            *reinterpret_cast<uint2*>(p16 + o + 32) = make_uint2((p[0] >> 16) | (p[1] & 0xffff0000u), (p[2] >> 16) | (p[3] & 0xffff0000u));
+            *reinterpret_cast<uint2*>(p16 + o + PL_LO) = make_uint2((p[0] >> 16) | (p[1] & 0xffff0000u), (p[2] >> 16) | (p[3] & 0xffff0000u));
         }
         if (pb != nullptr && c < ldb) {
             uint32_t p[4];
@@ -749,7 +723,7 @@ __global__ __launch_bounds__(256) void split_planes2_kernel(const float* __restr
             for (int k = 0; k < 4; ++k) p[k] = split_pack<__bf16>(v[k]);
             const size_t o = pl_off(r, c, ldb);
             *reinterpret_cast<uint2*>(pb + o) = make_uint2((p[0] & 0xffffu) | (p[1] << 16), (p[2] & 0xffffu) | (p[3] << 16));
-            *reinterpret_cast<uint2*>(pb + o + 32) = make_uint2((p[0] >> 16) | (p[1] & 0xffff0000u), (p[2] >> 16) | (p[3] & 0xffff0000u));
+            *reinterpret_cast<uint2*>(pb + o + PL_LO) = make_uint2((p[0] >> 16) | (p[1] & 0xffff0000u), (p[2] >> 16) | (p[3] & 0xffff0000u));
         }
     }
 }

@@ -19,10 +19,8 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef Vec<__bf16>::x8 bf16x8;
+typedef Vec<__bf16>::x4 bf16x4;
 
 struct MlpBwdArgs {
     const float* dZ; int lddz;
@@ -41,29 +39,14 @@ struct MlpBwdArgs {
 constexpr int mb_rows(bool dg) { return dg ? 64 : 32; }   // rows per block iteration (wide WGRAD: 128 accumulator registers)
 constexpr int MB_NT = 512;
 
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-__device__ __forceinline__ void split4(const float4& v, bf16x4& hi, bf16x4& lo) {
-    hi[0] = (__bf16)v.x; hi[1] = (__bf16)v.y; hi[2] = (__bf16)v.z; hi[3] = (__bf16)v.w;
-    lo[0] = (__bf16)(v.x - (float)hi[0]); lo[1] = (__bf16)(v.y - (float)hi[1]);
-    lo[2] = (__bf16)(v.z - (float)hi[2]); lo[3] = (__bf16)(v.w - (float)hi[3]);
-}
-
 // Fragment of a reduction-row operand stored row-major [reduction][columns] (16-bit): the lane of MFMA row
 // (lane & 31) and k half (lane >> 5) receives its 8 consecutive reduction values.  Inside a 16-lane group lane p supplies
 // the address of reduction row (p >> 2), columns 4 (p & 3) .. +3, and receives column p of the four rows.
 __device__ __forceinline__ bf16x8 tr_frag2(const char* p0, int pitch) {
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0));
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0 + 4 * pitch));
+    const s16x4 a = lds_tr(p0);
+    const s16x4 b = lds_tr(p0 + 4 * pitch);
     const s16x8 j = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, j);
-}
-
-__device__ __forceinline__ f32x16 mma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-    return acc;
 }
 
 // DGRAD epilogue of one 32x32 tile: quad transpose (a lane ends up with four consecutive columns of one row, see
@@ -77,14 +60,7 @@ __device__ __forceinline__ void dgrad_store(const MlpBwdArgs& a, const f32x16& a
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         float v0 = acc[4 * g + 0], v1 = acc[4 * g + 1], v2 = acc[4 * g + 2], v3 = acc[4 * g + 3];
-        {
-            const float s0 = (q & 1) ? v0 : v1, s1 = (q & 1) ? v2 : v3;
-            const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-            if (q & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-            const float t0 = (q & 2) ? v0 : v2, t1 = (q & 2) ? v1 : v3;
-            const float u0 = quad_xor2(t0), u1 = quad_xor2(t1);
-            if (q & 2) { v0 = u0; v1 = u1; } else { v2 = u0; v3 = u1; }
-        }
+        HOS_QUAD_TRANSPOSE4(v0, v1, v2, v3, q);
         const int lrow = q + 8 * g + 4 * lhi;                     // row inside the 32-row tile
         const int row = grow0 + lrow;
         if (row >= a.M || colb >= a.K) continue;
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
             const int u = t + MB_NT * i, row = u / (N_ / 4), c4 = u % (N_ / 4);
             bsum.x += rz[i].x; bsum.y += rz[i].y; bsum.z += rz[i].z; bsum.w += rz[i].w;   // c4 is the same for every i
             bf16x4 h, l;
-            split4(rz[i], h, l);
+            split4<__bf16>(rz[i], h, l);
             *reinterpret_cast<bf16x4*>(Zh + row * PZ + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Zl + row * PZ + c4 * 8) = l;
         }
@@ -168,7 +144,7 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
         for (int i = 0; i < XU; ++i) {
             const int u = t + MB_NT * i, row = u / (K_ / 4), c4 = u % (K_ / 4);
             bf16x4 h, l;
-            split4(rx[i], h, l);
+            split4<__bf16>(rx[i], h, l);
             *reinterpret_cast<bf16x4*>(Xh + row * PX + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Xl + row * PX + c4 * 8) = l;
         }
@@ -197,7 +173,7 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
                 const bf16x8 al = *reinterpret_cast<const bf16x8*>(zrow + Z_PLANE + s * 32);
                 const bf16x8 bh = tr_frag2(wfrag + s * 16 * PW, PW);
                 const bf16x8 bl = tr_frag2(wfrag + W_PLANE + s * 16 * PW, PW);
-                acc = mma3(ah, al, bh, bl, acc);
+                acc = mma3<__bf16>(ah, al, bh, bl, acc);
             }
         }
         // ---- WGRAD: dW[N_ x K_] += dZ^T[N_ x 64] . X[64 x K_]: tile (nt, kt) = wave + 8 j.  8 % KT == 0, so a wave's tiles
@@ -216,7 +192,7 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
                         const char* zfrag = Zh + tr_row * PZ + ((ti / KT) * 32 + tr_col) * 2;
                         const bf16x8 ah = tr_frag2(zfrag + s * 16 * PZ, PZ);
                         const bf16x8 al = tr_frag2(zfrag + Z_PLANE + s * 16 * PZ, PZ);
-                        accW[j] = mma3(ah, al, bh, bl, accW[j]);
+                        accW[j] = mma3<__bf16>(ah, al, bh, bl, accW[j]);
                     }
                 }
             }
@@ -240,7 +216,7 @@ __global__ __launch_bounds__(MB_NT, 1) void mlp_bwd_kernel(MlpBwdArgs a) {
         for (int i = 0; i < WU; ++i) {
             const int u = t + MB_NT * i, row = u / (K_ / 4), c4 = u % (K_ / 4);
             bf16x4 h, l;
-            split4(rw[i], h, l);
+            split4<__bf16>(rw[i], h, l);
             *reinterpret_cast<bf16x4*>(Wh + row * PW + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Wl + row * PW + c4 * 8) = l;
         }
@@ -367,7 +343,7 @@ __global__ __launch_bounds__(MB_NT, 1) void wgrad_tr_fast_kernel(MlpBwdArgs a) {
             const int u = t + MB_NT * i, row = u / (N_ / 4), c4 = u % (N_ / 4);
             bsum.x += rz[i].x; bsum.y += rz[i].y; bsum.z += rz[i].z; bsum.w += rz[i].w;   // c4 is the same for every i
             bf16x4 h, l;
-            split4(rz[i], h, l);
+            split4<__bf16>(rz[i], h, l);
             *reinterpret_cast<bf16x4*>(Zh + row * PZ + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Zl + row * PZ + c4 * 8) = l;
         }
@@ -376,7 +352,7 @@ __global__ __launch_bounds__(MB_NT, 1) void wgrad_tr_fast_kernel(MlpBwdArgs a) {
             for (int i = 0; i < XU; ++i) {
                 const int u = t + MB_NT * i, row = u / (K_ / 4), c4 = u % (K_ / 4);
                 bf16x4 h, l;
-                split4(rx[i], h, l);
+                split4<__bf16>(rx[i], h, l);
                 *reinterpret_cast<bf16x4*>(Xh + row * PX + c4 * 8) = h;
                 *reinterpret_cast<bf16x4*>(Xl + row * PX + c4 * 8) = l;
             }
@@ -400,7 +376,7 @@ __global__ __launch_bounds__(MB_NT, 1) void wgrad_tr_fast_kernel(MlpBwdArgs a) {
                 const char* zfrag = Zh + tr_row * PZ + ((ti / KT) * 32 + tr_col) * 2;
                 const bf16x8 ah = tr_frag2(zfrag + s * 16 * PZ, PZ);
                 const bf16x8 al = tr_frag2(zfrag + Z_PLANE + s * 16 * PZ, PZ);
-                accW[j] = mma3(ah, al, bh, bl, accW[j]);
+                accW[j] = mma3<__bf16>(ah, al, bh, bl, accW[j]);
             }
         }
     };
@@ -739,7 +715,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
             if (rb * R + row >= a.M) v = make_float4(0.f, 0.f, 0.f, 0.f);       // dead rows contribute nothing to any product
             bsum.x += v.x; bsum.y += v.y; bsum.z += v.z; bsum.w += v.w;          // c4 is the same for every i
             bf16x4 h, l;
-            split4(v, h, l);
+            split4<__bf16>(v, h, l);
             *reinterpret_cast<bf16x4*>(Zh + row * PZ + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Zh + R * PZ + row * PZ + c4 * 8) = l;
         }
@@ -765,7 +741,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
         for (int i = 0; i < XU; ++i) {
             const int u = t + MB_NT * i, row = u / (K_ / 4), c4 = u % (K_ / 4);
             bf16x4 h, l;
-            split4(rx[i], h, l);
+            split4<__bf16>(rx[i], h, l);
             *reinterpret_cast<bf16x4*>(Xh + row * PX + c4 * 8) = h;
             *reinterpret_cast<bf16x4*>(Xh + R * PX + row * PX + c4 * 8) = l;
         }
@@ -832,7 +808,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                         const bf16x8 al = *reinterpret_cast<const bf16x8*>(zrow + Z_PLANE + k * 32);
                         const bf16x8 bh = tr_frag2(wfrag + k * 16 * PW, PW);
                         const bf16x8 bl = tr_frag2(wfrag + W_PLANE + k * 16 * PW, PW);
-                        acc = mma3(ah, al, bh, bl, acc);
+                        acc = mma3<__bf16>(ah, al, bh, bl, acc);
                     }
                     loadW_part(std::integral_constant<int, SN>{}, k * RWN / NK, (k + 1) * RWN / NK);
                     __builtin_amdgcn_sched_barrier(0);
@@ -855,7 +831,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                                 const char* zfrag = Zh + tr_row * PZ + ((ti / KT) * 32 + tr_col) * 2;
                                 const bf16x8 ah = tr_frag2(zfrag + k * 16 * PZ, PZ);
                                 const bf16x8 al = tr_frag2(zfrag + Z_PLANE + k * 16 * PZ, PZ);
-                                accW[acc_off(s) + j] = mma3(ah, al, bh, bl, accW[acc_off(s) + j]);
+                                accW[acc_off(s) + j] = mma3<__bf16>(ah, al, bh, bl, accW[acc_off(s) + j]);
                             }
                         }
                     }
@@ -873,14 +849,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v0 = acc[4 * g + 0], v1 = acc[4 * g + 1], v2 = acc[4 * g + 2], v3 = acc[4 * g + 3];
-                    {
-                        const float s0 = (q & 1) ? v0 : v1, s1 = (q & 1) ? v2 : v3;
-                        const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-                        if (q & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-                        const float t0 = (q & 2) ? v0 : v2, t1 = (q & 2) ? v1 : v3;
-                        const float u0 = quad_xor2(t0), u1 = quad_xor2(t1);
-                        if (q & 2) { v0 = u0; v1 = u1; } else { v2 = u0; v3 = u1; }
-                    }
+                    HOS_QUAD_TRANSPOSE4(v0, v1, v2, v3, q);
                     v[g][0] = v0; v[g][1] = v1; v[g][2] = v2; v[g][3] = v3;
                     const int lrow = rt * 32 + q + 8 * g + 4 * lhi;              // row inside the block
                     if constexpr (cb_mask(code)) {
@@ -912,7 +881,7 @@ __global__ __launch_bounds__(MB_NT, 1) void chain_bwd_kernel(ChainBwdArgs a) {
                         for (int g = 0; g < 4; ++g) {
                             const int lrow = rt * 32 + q + 8 * g + 4 * lhi;
                             bf16x4 h, l;
-                            split4(make_float4(v[g][0], v[g][1], v[g][2], v[g][3]), h, l);
+                            split4<__bf16>(make_float4(v[g][0], v[g][1], v[g][2], v[g][3]), h, l);
                             *reinterpret_cast<bf16x4*>(Zh + lrow * PZn + colb * 2) = h;
                             *reinterpret_cast<bf16x4*>(Zh + R * PZn + lrow * PZn + colb * 2) = l;
                         }
@@ -999,9 +968,9 @@ __global__ __launch_bounds__(256) void chain_bwd_pack_kernel(const ChainBwdPackJ
         const int n = r / pw, k = r % pw;
         uint16_t out = 0;
         if (plane < 2 && n < J.N && k < J.K) {
-            const float w = J.W[(size_t)n * J.ldw + k];
-            const __bf16 hi = (__bf16)w;
-            out = plane == 0 ? __builtin_bit_cast(uint16_t, hi) : __builtin_bit_cast(uint16_t, (__bf16)(w - (float)hi));
+            __bf16 hi, lo;
+            split1<__bf16>(J.W[(size_t)n * J.ldw + k], hi, lo);
+            out = __builtin_bit_cast(uint16_t, plane == 0 ? hi : lo);
         }
         J.image[e] = out;
     }

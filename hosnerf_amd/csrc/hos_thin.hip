@@ -21,24 +21,6 @@ namespace {
 constexpr int TH_PF2_MAXKS = 16;     // fast forward kernel: two tiles of register prefetch up to this many reduction steps
 constexpr int TH_R_FWD = 32;         // rows per forward tile (64 measured 3-5 % slower once the epilogue stopped loading the bias)
 
-template <typename E> struct V8 { typedef E t __attribute__((ext_vector_type(8))); typedef E q __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ f32x16 mfma_e(const V8<__bf16>::t& a, const V8<__bf16>::t& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma_e(const V8<_Float16>::t& a, const V8<_Float16>::t& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-template <typename E> __device__ __forceinline__ float hi_of(float x) { return x; }
-// (one v_med3_f32; fminf(fmaxf()) costs a canonicalising v_max in front of it: 16 more VALU per staged tile and thread)
-template <> __device__ __forceinline__ float hi_of<_Float16>(float x) { return __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
-
-template <typename E>
-__device__ __forceinline__ void split_pair(float x, E& hi, E& lo) {
-    hi = (E)hi_of<E>(x);
-    lo = (E)(x - (float)hi);
-}
-
 struct ThinArgs {
     const float* A; int lda;          // activations (FWD: layer input; DGRAD: dZ)
     const float* W; int ldw;          // nn.Linear weight [Nout_fwd, ldw]
@@ -67,15 +49,14 @@ constexpr int TH_NT = 512;
 constexpr int TH_PAD_DGRAD = 16, TH_PAD_FWD = 32;
 template <bool DGRAD> constexpr int th_pad() { return DGRAD ? TH_PAD_DGRAD : TH_PAD_FWD; }
 constexpr int TH_MP = 264;     // LDS pitch of a mask row: 256 columns + the 16-byte group a window at an unaligned column spills into
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // KS: reduction steps of 16 (K <= 16 KS).  R: rows per tile (64 FWD, 32 DGRAD: the mask tile needs the registers).
 template <int KS, bool DGRAD>
 __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
     if (a.m_dev) a.M = min(a.M, *a.m_dev);               // every row test below then stops at the live rows
     typedef typename std::conditional<DGRAD, __bf16, _Float16>::type E;
-    typedef typename V8<E>::t e8;
-    typedef typename V8<E>::q e4;
+    typedef typename Vec<E>::x8 e8;
+    typedef typename Vec<E>::x4 e4;
     constexpr int R = DGRAD ? 32 : TH_R_FWD;
     constexpr int KD = KS * 16;
     constexpr int P = KD * 2 + th_pad<DGRAD>();          // LDS row pitch of one plane (bytes), see th_pad
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
             if (j < a.N) {
                 if constexpr (!DGRAD) {
                     if (k0 + 7 < a.K) {
-                        const float4 u = ld4(a.W + (size_t)j * a.ldw + k0), v = ld4(a.W + (size_t)j * a.ldw + k0 + 4);
+                        const float4 u = ldg4(a.W + (size_t)j * a.ldw + k0), v = ldg4(a.W + (size_t)j * a.ldw + k0 + 4);
                         w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w; w[4] = v.x; w[5] = v.y; w[6] = v.z; w[7] = v.w;
                     } else {
 #pragma unroll
@@ -118,7 +99,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
                 }
             }
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { E h, l; split_pair<E>(w[q], h, l); bh[s][q] = h; bl[s][q] = l; }
+            for (int q = 0; q < 8; ++q) { E h, l; split1<E>(w[q], h, l); bh[s][q] = h; bl[s][q] = l; }
         }
     }
 
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
         for (int i = 0; i < AU; ++i) {
             const int u = t + TH_NT * i, row = u / (KD / 4), c4 = u % (KD / 4);
             const int gr = tile * R + row;
-            ra[i] = (gr < a.M && c4 * 4 < a.K) ? ld4(a.A + (size_t)gr * a.lda + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ra[i] = (gr < a.M && c4 * 4 < a.K) ? ldg4(a.A + (size_t)gr * a.lda + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         if constexpr (DGRAD) {
             if (a.bits != nullptr) rbits = a.bits[(size_t)tile * TH_NT + t];
@@ -146,11 +127,11 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
                 for (int i = 0; i < MU; ++i) {
                     const int u = t + TH_NT * i, row = u >> 6, c4 = u & 63;
                     const int gr = tile * R + row;
-                    rm[i] = (gr < a.M && c4 * 4 < a.N + msh) ? ld4(mbase + (size_t)gr * a.ldmask + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    rm[i] = (gr < a.M && c4 * 4 < a.N + msh) ? ldg4(mbase + (size_t)gr * a.ldmask + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
                 if (msh != 0 && t < R) {
                     const int gr = tile * R + t;
-                    rmx = (gr < a.M && 256 < a.N + msh) ? ld4(mbase + (size_t)gr * a.ldmask + 256) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    rmx = (gr < a.M && 256 < a.N + msh) ? ldg4(mbase + (size_t)gr * a.ldmask + 256) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
         }
@@ -164,7 +145,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
             e4 h, l;
             const float xs[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { E hh, ll; split_pair<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
+            for (int q = 0; q < 4; ++q) { E hh, ll; split1<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
             *reinterpret_cast<e4*>(hi + row * P + c4 * 8) = h;
             *reinterpret_cast<e4*>(lo + row * P + c4 * 8) = l;
         }
@@ -222,9 +203,10 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
             for (int rt = 0; rt < R / 32; ++rt) {
                 const e8 ah = *reinterpret_cast<const e8*>(hi + rt * 32 * P + s * 32);
                 const e8 al = *reinterpret_cast<const e8*>(hi + PLANE + rt * 32 * P + s * 32);
-                acc[rt] = mfma_e(al, bh[s], acc[rt]);
-                acc[rt] = mfma_e(ah, bl[s], acc[rt]);
-                acc[rt] = mfma_e(ah, bh[s], acc[rt]);
+                // (open-coded mma3: through the shared function all three kernels of this file come out with another schedule)
+                acc[rt] = mfma16(al, bh[s], acc[rt]);
+                acc[rt] = mfma16(ah, bl[s], acc[rt]);
+                acc[rt] = mfma16(ah, bh[s], acc[rt]);
             }
         }
         // Stage the next tile BEFORE this tile's stores: vmcnt retires in order, so converting the prefetched registers
@@ -247,14 +229,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         float v0 = acc[rt][4 * g + 0], v1 = acc[rt][4 * g + 1], v2 = acc[rt][4 * g + 2], v3 = acc[rt][4 * g + 3];
-                        {
-                            const float s0 = (q & 1) ? v0 : v1, s1 = (q & 1) ? v2 : v3;
-                            const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-                            if (q & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-                            const float t0 = (q & 2) ? v0 : v2, t1 = (q & 2) ? v1 : v3;
-                            const float u0 = quad_xor2(t0), u1 = quad_xor2(t1);
-                            if (q & 2) { v0 = u0; v1 = u1; } else { v2 = u0; v3 = u1; }
-                        }
+                        HOS_QUAD_TRANSPOSE4(v0, v1, v2, v3, q);
                         const int lrow = q + 8 * g + 4 * lhi, row = row0 + lrow;
                         if (row >= a.M || colb >= a.N) continue;
                         float v[4] = {v0, v1, v2, v3};
@@ -299,8 +274,8 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_gemm_kernel(ThinArgs a) {
 template <int KS, bool BITS>
 __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs a) {
     typedef _Float16 E;
-    typedef typename V8<E>::t e8;
-    typedef typename V8<E>::q e4;
+    typedef typename Vec<E>::x8 e8;
+    typedef typename Vec<E>::x4 e4;
     constexpr int R = 32;
     const int ntiles = th_live_tiles(a);
     if ((int)blockIdx.x >= ntiles) return;               // block-uniform, before the first barrier (also: no live row at all)
@@ -323,14 +298,14 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
         const float* wrow = a.W + (size_t)(col0 + l31) * a.ldw + 8 * lhi;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            const float4 u = ld4(wrow + 16 * s), v = ld4(wrow + 16 * s + 4);
+            const float4 u = ldg4(wrow + 16 * s), v = ldg4(wrow + 16 * s + 4);
             const float w[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { E h, l; split_pair<E>(w[q], h, l); bh[s][q] = h; bl[s][q] = l; }
+            for (int q = 0; q < 8; ++q) { E h, l; split1<E>(w[q], h, l); bh[s][q] = h; bl[s][q] = l; }
         }
     }
     const int q4 = l31 & 3, colb = col0 + (l31 & ~3);
-    const float4 bias4 = a.bias != nullptr ? ld4(a.bias + colb) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 bias4 = a.bias != nullptr ? ldg4(a.bias + colb) : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool relu = a.epi == HOS_EPI_RELU;
 
     const int G = gridDim.x;
@@ -342,7 +317,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
 #pragma unroll
         for (int i = 0; i < AU; ++i) {
             const int u = t + TH_NT * i, row = u / (KD / 4), c4 = u % (KD / 4);
-            r[i] = ld4(base + (size_t)row * a.lda + c4 * 4);
+            r[i] = ldg4(base + (size_t)row * a.lda + c4 * 4);
         }
     };
     auto sstore = [&](const float4 (&r)[AU], int b) {
@@ -354,7 +329,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
             e4 h, l;
             const float xs[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { E hh, ll; split_pair<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
+            for (int q = 0; q < 4; ++q) { E hh, ll; split1<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
             *reinterpret_cast<e4*>(hi + row * P + c4 * 8) = h;
             *reinterpret_cast<e4*>(lo + row * P + c4 * 8) = l;
         }
@@ -379,9 +354,9 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
         for (int s = 0; s < KS; ++s) {
             const e8 ah = *reinterpret_cast<const e8*>(hi + s * 32);
             const e8 al = *reinterpret_cast<const e8*>(hi + PLANE + s * 32);
-            acc = mfma_e(al, bh[s], acc);
-            acc = mfma_e(ah, bl[s], acc);
-            acc = mfma_e(ah, bh[s], acc);
+            acc = mfma16(al, bh[s], acc);
+            acc = mfma16(ah, bl[s], acc);
+            acc = mfma16(ah, bh[s], acc);
         }
         if (more) sstore(rcur, b ^ 1);                  // the wait for `rcur` sits here: vmcnt(number of younger operations)
         gload(rcur, tile + PFD * G);
@@ -391,14 +366,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v0 = acc[4 * g + 0], v1 = acc[4 * g + 1], v2 = acc[4 * g + 2], v3 = acc[4 * g + 3];
-            {   // 4x4 transpose inside the quad (as gemm_epilogue_tile): afterwards (v0..v3) = row q4, columns colb .. colb+3
-                const float s0 = (q4 & 1) ? v0 : v1, s1 = (q4 & 1) ? v2 : v3;
-                const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-                if (q4 & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-                const float t0 = (q4 & 2) ? v0 : v2, t1 = (q4 & 2) ? v1 : v3;
-                const float u0 = quad_xor2(t0), u1 = quad_xor2(t1);
-                if (q4 & 2) { v0 = u0; v1 = u1; } else { v2 = u0; v3 = u1; }
-            }
+            HOS_QUAD_TRANSPOSE4(v0, v1, v2, v3, q4);        // afterwards (v0..v3) = row q4, columns colb .. colb+3
             float v[4] = {v0 + bias4.x, v1 + bias4.y, v2 + bias4.z, v3 + bias4.w};
             if constexpr (BITS) {        // four bits per row group, an independent chain each (bit 15 - (4 g + k) = element k of group g)
                 uint32_t m = 0;
@@ -454,8 +422,8 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_fwd_fast_kernel(const ThinArgs 
 template <bool MASK>
 __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArgs a) {
     typedef __bf16 E;
-    typedef typename V8<E>::t e8;
-    typedef typename V8<E>::q e4;
+    typedef typename Vec<E>::x8 e8;
+    typedef typename Vec<E>::x4 e4;
     constexpr int KS = 16, R = 32;
     const int ntiles = th_live_tiles(a);
     if ((int)blockIdx.x >= ntiles) return;               // block-uniform, before the first barrier
@@ -480,7 +448,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
-            for (int q = 0; q < 8; ++q) { E h, l; split_pair<E>(wcol[(size_t)(16 * s + q) * a.ldw], h, l); bh[s][q] = h; bl[s][q] = l; }
+            for (int q = 0; q < 8; ++q) { E h, l; split1<E>(wcol[(size_t)(16 * s + q) * a.ldw], h, l); bh[s][q] = h; bl[s][q] = l; }
     }
     const int q4 = l31 & 3, colb = col0 + (l31 & ~3);
     const int G = gridDim.x;
@@ -492,7 +460,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
 #pragma unroll
         for (int i = 0; i < AU; ++i) {
             const int u = t + TH_NT * i, row = u / (KD / 4), c4 = u % (KD / 4);
-            r[i] = ld4(base + (size_t)row * a.lda + c4 * 4);
+            r[i] = ldg4(base + (size_t)row * a.lda + c4 * 4);
         }
         if constexpr (MASK) rbits = a.bits[(size_t)tile * TH_NT + t];
     };
@@ -505,7 +473,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
             e4 h, l;
             const float xs[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { E hh, ll; split_pair<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
+            for (int q = 0; q < 4; ++q) { E hh, ll; split1<E>(xs[q], hh, ll); h[q] = hh; l[q] = ll; }
             *reinterpret_cast<e4*>(hi + row * P + c4 * 8) = h;
             *reinterpret_cast<e4*>(lo + row * P + c4 * 8) = l;
         }
@@ -530,9 +498,9 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
             for (int s = 0; s < KS; ++s) {
                 const e8 ah = *reinterpret_cast<const e8*>(hi + s * 32);
                 const e8 al = *reinterpret_cast<const e8*>(hi + PLANE + s * 32);
-                acc = mfma_e(al, bh[s], acc);
-                acc = mfma_e(ah, bl[s], acc);
-                acc = mfma_e(ah, bh[s], acc);
+                acc = mfma16(al, bh[s], acc);
+                acc = mfma16(ah, bl[s], acc);
+                acc = mfma16(ah, bh[s], acc);
             }
         }
         if (more) sstore(rcur, bcur, b ^ 1);
@@ -542,14 +510,7 @@ __global__ __launch_bounds__(TH_NT, 1) void thin_dgrad_fast_kernel(const ThinArg
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v0 = acc[4 * g + 0], v1 = acc[4 * g + 1], v2 = acc[4 * g + 2], v3 = acc[4 * g + 3];
-            {   // 4x4 transpose inside the quad: afterwards (v0..v3) = row q4 + 8 g + 4 lhi, columns colb .. colb+3
-                const float s0 = (q4 & 1) ? v0 : v1, s1 = (q4 & 1) ? v2 : v3;
-                const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-                if (q4 & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-                const float t0 = (q4 & 2) ? v0 : v2, t1 = (q4 & 2) ? v1 : v3;
-                const float u0 = quad_xor2(t0), u1 = quad_xor2(t1);
-                if (q4 & 2) { v0 = u0; v1 = u1; } else { v2 = u0; v3 = u1; }
-            }
+            HOS_QUAD_TRANSPOSE4(v0, v1, v2, v3, q4);        // afterwards (v0..v3) = row q4 + 8 g + 4 lhi, columns colb .. colb+3
             float v[4] = {v0, v1, v2, v3};
             if constexpr (MASK) {
 #pragma unroll
