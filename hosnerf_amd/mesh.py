@@ -76,7 +76,20 @@ box may reach beyond the unit ball, the contraction takes any point; the default
 the contraction leaves linear.  The zero rim closes the surface, so WHERE THE BOX CUTS SOLID MATTER (the ground, a wall) THE MESH IS
 CAPPED by faces on the box's walls: they are the box, not the scene.  The NeRF MLP's colour depends on the view direction: the
 vertex colours come from a second query at the mesh vertices, each seen head-on (view direction = -normal; (0,0,-1) where the normal
-is the zero vector).  Level 0.5 and resolution 256 are the same parameters, as unmeasured on a real scene as for the other two meshes."""
+is the zero vector).  Level 0.5 and resolution 256 are the same parameters, as unmeasured on a real scene as for the other two meshes.
+
+Mesh components (`components`, `drop_floaters`; hos_components.hip): on a NeRF density field marching tetrahedra gives the subject or
+the scene PLUS FLOATERS, small closed blobs of stray density, and every measure above counts them as if they were the object.  Two
+vertices are connected when a face names both; `components` labels every vertex with the smallest vertex id of its connected
+component (a definition that fixes the result whatever the GPU's scheduling), numbers the components densely by ascending root, and
+measures each: vertices, faces, area, signed volume -- a NEGATIVE volume is the inner wall of a hollow, reported by its sign and
+otherwise a component like any other.  `drop_floaters` keeps component c iff n_faces[c] >= min_faces and area[c] >= min_area_ratio *
+max(area) and compacts the mesh to the kept ones in their original order.  The extractors take the same two thresholds
+(`min_area_ratio`, `min_faces`; both 0 = nothing is labelled, the mesh is what it always was) and filter BEFORE the per-vertex work:
+`extract_frame` before the normals and `to_space`, `extract_bkgd` before the colour query, so the NeRF MLP never runs on a dropped
+vertex.  Normals and colours are functions of the vertex alone, so the kept vertices get the values they would have had.  A faces
+row with a corner outside [0, V) is ignored and counted (`invalid_faces`).  Out of scope: filling cavities, merging components,
+correspondence of components across frames; `track` tracks whatever template it is given."""
 from __future__ import annotations
 
 import contextlib
@@ -155,19 +168,100 @@ def mesh_measures(vertices: torch.Tensor, faces: torch.Tensor):
     return float(volume), float(area)
 
 
-def extract(net, turn, time: float, resolution: int = 256, level: float = 0.5, chunk: int = 1 << 18, normals: bool = False) -> Dict:
+def _mesh_tensors(what: str, vertices, faces):
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{what}: vertices must be a float32 tensor [V,3], got {getattr(vertices, 'dtype', type(vertices))} "
+                         f"{tuple(getattr(vertices, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be an int32 tensor [F,3], got {getattr(faces, 'dtype', type(faces))} "
+                         f"{tuple(getattr(faces, 'shape', ()))}")
+    if faces.device != vertices.device:
+        raise ValueError(f"{what}: vertices are on {vertices.device}, faces on {faces.device}")
+    return vertices.contiguous(), faces.contiguous()
+
+
+def components(vertices: torch.Tensor, faces: torch.Tensor) -> Dict:
+    """The connected components of a triangle mesh on the device (`vertices` f32 [V,3], `faces` int32 [F,3]: a marched mesh, a tracked
+    one, one read back with `formats.read_ply`): `label` int32 [V] (the smallest vertex id of the vertex's component), `component`
+    int32 [V] (dense ids by ascending root), `face_component` int32 [F] (-1 for a face with a corner outside [0,V), which every
+    kernel ignores), `count`, per component `n_vertices` / `n_faces` int64 [C] and `area` / `volume` float64 [C] (the terms of
+    `mesh_measures`; bit-equal from run to run), `rounds` (hook + jump rounds the labelling took, the last one changing nothing)
+    and `invalid_faces`.  `ops.mesh_label` then `ops.mesh_component_measures`; a vertex no face names is a component of its own."""
+    vertices, faces = _mesh_tensors("components", vertices, faces)
+    label, component, count, rounds, invalid = ops.mesh_label(faces, vertices.shape[0])
+    face_component, n_vertices, n_faces, area, volume = ops.mesh_component_measures(vertices, faces, component, count)
+    return {"label": label, "component": component, "face_component": face_component, "count": count, "n_vertices": n_vertices,
+            "n_faces": n_faces, "area": area, "volume": volume, "rounds": rounds, "invalid_faces": invalid}
+
+
+def _thresholds(what: str, min_area_ratio, min_faces):
+    r, n = float(min_area_ratio), int(min_faces)
+    if not (0.0 <= r <= 1.0) or n < 0 or n != min_faces:
+        raise ValueError(f"{what}: min_area_ratio {min_area_ratio!r} must lie in [0, 1] and min_faces {min_faces!r} be an integer >= 0")
+    return r, n
+
+
+def keep_flags(comp: Dict, min_area_ratio: float = 0.0, min_faces: int = 0) -> torch.Tensor:
+    """uint8 [C]: component c of `comp` (`components`) is kept iff n_faces[c] >= min_faces and area[c] >= min_area_ratio * max(area)."""
+    r, n = _thresholds("keep_flags", min_area_ratio, min_faces)
+    area = comp["area"]
+    if area.numel() == 0:
+        return torch.zeros(0, dtype=torch.uint8, device=area.device)
+    return ((comp["n_faces"] >= n) & (area >= r * area.max())).to(torch.uint8)
+
+
+def drop_floaters(m: Dict, min_area_ratio: float = 0.0, min_faces: int = 0) -> Dict:
+    """The mesh dict `m` (as `extract` / `extract_frame` / `extract_bkgd` return it) without its floaters: component c is kept iff
+    n_faces[c] >= min_faces and area[c] >= min_area_ratio * max(area).  With both thresholds 0 this is `m` itself, nothing is launched.
+    Otherwise a copy whose `vertices`, `faces`, `colors` and `normals` are compacted to the kept components (`ops.mesh_compact`:
+    original order, faces renumbered), `volume` / `area` recomputed by `mesh_measures`, and `components` added: `count`, `kept`,
+    `V_dropped`, `F_dropped`, `area_dropped`, `volume_dropped`, `rounds`, `invalid_faces`, `negative_volume` (how many components
+    have a negative volume: inner walls of hollows, kept or dropped by the same rule as any other).  A `body` mesh (`extract_frame(
+    keep_body=True)`: the same topology) gets the same keep flags, the labelling runs once; `vertex_rgb` (`extract_bkgd`) is gathered
+    like the normals.  Every other entry -- the field `alpha` /
+    `rgb`, the grid, `state` -- passes through untouched."""
+    r, n = _thresholds("drop_floaters", min_area_ratio, min_faces)
+    if r == 0.0 and n == 0:
+        return m
+    vertices, faces = _mesh_tensors("drop_floaters", m["vertices"], m["faces"])
+    comp = components(vertices, faces)
+    keep = keep_flags(comp, r, n)
+    pick = lambda d: ops.mesh_compact(keep, comp["component"], comp["face_component"], d["vertices"].contiguous(), d["faces"].contiguous(),
+                                      d.get("colors"), d.get("normals"))
+    out = dict(m)
+    out["vertices"], out["faces"], out["colors"], out["normals"] = pick(m)
+    out["volume"], out["area"] = mesh_measures(out["vertices"], out["faces"])
+    if m.get("vertex_rgb") is not None:                     # `extract_bkgd`'s colours before truncation: per vertex, like the normals
+        out["vertex_rgb"] = ops.mesh_compact(keep, comp["component"], comp["face_component"], vertices, faces, None, m["vertex_rgb"].contiguous())[3]
+    if m.get("body") is not None:
+        body = dict(m["body"])
+        body["vertices"], body["faces"], body["colors"], body["normals"] = pick(m["body"])
+        out["body"] = body
+    gone = keep == 0
+    out["components"] = {"count": int(comp["count"]), "kept": int(keep.sum()), "V_dropped": int(vertices.shape[0] - out["vertices"].shape[0]),
+                         "F_dropped": int(faces.shape[0] - out["faces"].shape[0]), "area_dropped": float(comp["area"][gone].sum()),
+                         "volume_dropped": float(comp["volume"][gone].sum()), "rounds": int(comp["rounds"]),
+                         "invalid_faces": int(comp["invalid_faces"]), "negative_volume": int((comp["volume"] < 0).sum())}
+    return out
+
+
+def extract(net, turn, time: float, resolution: int = 256, level: float = 0.5, chunk: int = 1 << 18, normals: bool = False,
+            min_area_ratio: float = 0.0, min_faces: int = 0) -> Dict:
     """The mesh of the canonical human-object at `time`'s object state: `canonical_field` on `turn` (a `tpose.TposeTurn`: canonical
     box, joints and priors), then `ops.march_tets` at `level`.  Returns `vertices` f32 [V,3], `faces` int32 [F,3] and `colors` uint8
     [V,3] (the 8-bit truncation of `to_8b_image`) on the device, `origin`, `spacing`, `dims`, `state`, the signed `volume` and
     the `area` as floats, and the field it was extracted from (`alpha` [Nz,Ny,Nx], `rgb` [Nz,Ny,Nx,3]).  `level` and `resolution` are unmeasured defaults (module docstring).
-    `normals=True` adds `normals` f32 [V,3] (`ops.mesh_vertex_normals`; `None` otherwise); nothing else changes."""
+    `normals=True` adds `normals` f32 [V,3] (`ops.mesh_vertex_normals`; `None` otherwise); nothing else changes.
+    `min_area_ratio` / `min_faces` above 0: `drop_floaters` of the result (adds `components`); at 0 the path is exactly the above."""
+    _thresholds("extract", min_area_ratio, min_faces)
     field = canonical_field(net, turn.const, time, resolution, chunk)
     vertices, colors, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"], rgb=field["rgb"])
     volume, area = mesh_measures(vertices, faces)
-    return {"vertices": vertices, "faces": faces, "colors": (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
-            "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
-            "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"],
-            "normals": ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None}
+    out = {"vertices": vertices, "faces": faces, "colors": (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
+           "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
+           "level": float(level), "alpha": field["alpha"], "rgb": field["rgb"],
+           "normals": ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None}
+    return drop_floaters(out, min_area_ratio, min_faces)
 
 
 # ------------------------------------------------------------------------------------------ the frame mesh
@@ -257,7 +351,7 @@ def to_space(vertices: torch.Tensor, faces: torch.Tensor, normals, A) -> tuple:
 
 
 def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, space: str = "world", normals: bool = False,
-                  chunk: int = 1 << 18, keep_body: bool = False) -> Dict:
+                  chunk: int = 1 << 18, keep_body: bool = False, min_area_ratio: float = 0.0, min_faces: int = 0) -> Dict:
     """The mesh of the human-object as it stands in the frame of `pose` (`dataset.SceneItems.frame_pose`): `frame_field`, then
     `ops.march_tets` at `level`.  Returns what `extract` returns (`origin`, `spacing`, `dims` and the field `alpha` / `rgb` are the
     body-frame grid's) plus `space`, `to_world` (float32 [4,4] host array: `pose["newsmpl_to_scale_world"]`, the body frame -> the
@@ -265,9 +359,12 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
     `space="world"` writes the vertices (and turns the normals) by `to_space`; `volume` and `area` are those of the returned
     vertices.  `level` and `resolution` are unmeasured defaults (module docstring).  `keep_body=True` adds `body`: the mesh BEFORE
     `to_space` (`vertices`, `faces`, `colors`, `normals` in the body frame, the space of the frame's rays: what `rasterize` takes
-    with `SceneItems.frame_camera`), the very tensors for `space="body"`; nothing else changes."""
+    with `SceneItems.frame_camera`), the very tensors for `space="body"`; nothing else changes.
+    `min_area_ratio` / `min_faces` above 0: the marched mesh goes through `drop_floaters` BEFORE the normals and `to_space` (so `body`
+    is the filtered mesh too) and `components` is added; at 0 the path is exactly the above."""
     if space not in SPACES:
         raise ValueError(f"extract_frame: space {space!r} is not one of {SPACES}")
+    filtering = _thresholds("extract_frame", min_area_ratio, min_faces) != (0.0, 0)
     to_world = np.eye(4, dtype=np.float32)
     if space == "world":
         if pose.get("newsmpl_to_scale_world") is None:
@@ -277,8 +374,12 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
         to_world = np.ascontiguousarray(A.detach().cpu().numpy() if hasattr(A, "detach") else A, dtype=np.float32).reshape(4, 4)
     field = frame_field(net, pose, resolution, chunk)
     vertices, colors, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"], rgb=field["rgb"])
-    vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None
     colors8 = (255.0 * colors.clamp(0.0, 1.0)).to(torch.uint8)
+    kept = None
+    if filtering:
+        kept = drop_floaters({"vertices": vertices, "faces": faces, "colors": colors8, "normals": None}, min_area_ratio, min_faces)
+        vertices, faces, colors8 = kept["vertices"], kept["faces"], kept["colors"]
+    vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices) if normals else None
     body = {"vertices": vertices, "faces": faces, "colors": colors8, "normals": vn} if keep_body else None
     if space == "world":
         vertices, faces, vn = to_space(vertices, faces, vn, to_world)
@@ -290,6 +391,8 @@ def extract_frame(net, pose: Dict, resolution: int = 256, level: float = 0.5, sp
            "frame_name": pose.get("frame_name"), "time": None if time is None else float(time)}
     if keep_body:
         out["body"] = body
+    if kept is not None:
+        out["components"] = kept["components"]
     return out
 
 
@@ -484,16 +587,24 @@ def head_on_viewdirs(normals: torch.Tensor) -> torch.Tensor:
     return torch.where(zero, torch.tensor(HEAD_ON_FALLBACK, device=normals.device).expand_as(normals), -normals).contiguous()
 
 
-def extract_bkgd(model, box, time: float, resolution: int = 256, level: float = 0.5, normals: bool = True, chunk: int = 1 << 18) -> Dict:
+def extract_bkgd(model, box, time: float, resolution: int = 256, level: float = 0.5, normals: bool = True, chunk: int = 1 << 18,
+                 min_area_ratio: float = 0.0, min_faces: int = 0) -> Dict:
     """The mesh of the background at `time`'s object state inside `box`: `bkgd_field`, `ops.march_tets` at `level`,
     `ops.mesh_vertex_normals`, then the colours from a second `query_points` at the vertices (same var, view direction
     `head_on_viewdirs`).  Returns what `extract` returns -- `vertices` f32 [V,3] in the background rays' space (the scaled world),
     `faces` int32 [F,3], `colors` uint8 [V,3] (the truncation of `to_8b_image`), `normals` f32 [V,3] (None with `normals=False`: they
     are computed regardless, the colours need them), `origin`, `spacing`, `dims`, `state`, `volume`, `area`, `level`, `alpha` -- plus
     `vertex_rgb` f32 [V,3] (the colours before truncation), `density`, `var` and `box`.  `level` and `resolution` are unmeasured
-    defaults; the surface is capped where the box cuts solid matter (module docstring)."""
+    defaults; the surface is capped where the box cuts solid matter (module docstring).
+    `min_area_ratio` / `min_faces` above 0: the marched mesh goes through `drop_floaters` BEFORE the normals and the colour query, so
+    the NeRF MLP does not run on a dropped vertex, and `components` is added; at 0 the path is exactly the above."""
+    filtering = _thresholds("extract_bkgd", min_area_ratio, min_faces) != (0.0, 0)
     field = bkgd_field(model, box, time, resolution, chunk)
     vertices, _, faces = ops.march_tets(field["alpha"], level, field["origin"], field["spacing"])
+    kept = None
+    if filtering:
+        kept = drop_floaters({"vertices": vertices, "faces": faces, "colors": None, "normals": None}, min_area_ratio, min_faces)
+        vertices, faces = kept["vertices"], kept["faces"]
     vn = ops.mesh_vertex_normals(field["alpha"], field["origin"], field["spacing"], vertices)
     V = vertices.shape[0]
     dev = vertices.device
@@ -510,10 +621,13 @@ def extract_bkgd(model, box, time: float, resolution: int = 256, level: float = 
         with _evaluating_bkgd(model):
             ops.guarded_forward(model, dev, run)
     volume, area = mesh_measures(vertices, faces)
-    return {"vertices": vertices, "faces": faces, "colors": (255.0 * rgb.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
-            "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
-            "level": float(level), "alpha": field["alpha"], "normals": vn if normals else None, "vertex_rgb": rgb,
-            "density": field["density"], "var": field["var"], "box": field["box"]}
+    out = {"vertices": vertices, "faces": faces, "colors": (255.0 * rgb.clamp(0.0, 1.0)).to(torch.uint8), "origin": field["origin"],
+           "spacing": float(field["spacing"]), "dims": field["dims"], "state": int(field["state"]), "volume": volume, "area": area,
+           "level": float(level), "alpha": field["alpha"], "normals": vn if normals else None, "vertex_rgb": rgb,
+           "density": field["density"], "var": field["var"], "box": field["box"]}
+    if kept is not None:
+        out["components"] = kept["components"]
+    return out
 
 
 # ------------------------------------------------------------------------------------------ the meshes seen again: raster and fit

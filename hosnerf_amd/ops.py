@@ -2277,3 +2277,122 @@ def frame_fit(mask_a, depth_a, alpha_b, depth_b, tau: float = 0.5) -> torch.Tens
     call("hos_frame_fit", ptr(mask_a, torch.uint8) if n else 0, ptr(depth_a) if n else 0, ptr(alpha_b) if n else 0, ptr(depth_b) if n else 0,
          float(tau), n, ptr(ws, torch.int64), out.data_ptr(), out.data_ptr() + 24)
     return out
+
+
+# ------------------------------------------------------------------------------------------ mesh components (hos_components.hip)
+def _mesh_faces_check(what: str, faces, V=None):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise _lib.HosLibraryError(f"{what}: faces must be int32 [F,3], got {getattr(faces, 'dtype', type(faces))} {tuple(getattr(faces, 'shape', ()))}")
+    if V is not None and (int(V) < 0 or int(V) >= 2 ** 31 - 256 or faces.shape[0] >= 2 ** 31 - 256):
+        raise _lib.HosLibraryError(f"{what}: V {V} / F {faces.shape[0]} must lie in [0, 2^31 - 256) (ids are int32)")
+
+
+def mesh_label(faces, V: int, max_rounds=None):
+    """The connected components of the mesh `faces` int32 [F,3] over `V` vertices -> (label int32 [V], component int32 [V], count,
+    rounds, invalid_faces): label[v] = the smallest vertex id of v's component, component[v] = the rank of that id among the roots
+    in ascending order, `count` of them; `invalid_faces` faces with a corner outside [0,V) were ignored (include/hosrender.h).
+    Rounds of hook + jump launches (hos_mesh_label_round) until one changes nothing, one 16-byte read-back per round, then the dense
+    ids and one more read-back; more than `max_rounds` (default and at most V + 2, the bound of plain min-propagation) rounds raise
+    `HosLibraryError`.  V = 0 returns empty tensors without a launch."""
+    V = int(V)
+    _mesh_faces_check("mesh_label", faces, V)
+    cap = V + 2 if max_rounds is None else min(int(max_rounds), V + 2)
+    dev = faces.device
+    F = int(faces.shape[0])
+    if V == 0:
+        empty = torch.empty(0, dtype=torch.int32, device=dev)
+        return empty, empty.clone(), 0, 0, F
+    _lib.require_gpu()
+    label = torch.empty(V, dtype=torch.int32, device=dev)
+    component = torch.empty(V, dtype=torch.int32, device=dev)
+    words = torch.empty(4, dtype=torch.int32, device=dev)
+    call("hos_mesh_label_begin", V, ptr(label, torch.int32), ptr(words, torch.int32))
+    rounds = 0
+    while F > 0:
+        if rounds >= cap:
+            raise _lib.HosLibraryError(f"mesh_label: no fixed point after {rounds} rounds (V = {V}, F = {F}; the bound is V + 2)")
+        call("hos_mesh_label_round", ptr(faces, torch.int32), F, V, rounds, ptr(label, torch.int32), ptr(words, torch.int32))
+        changed = words.tolist()[1 + (rounds & 1)]        # the read-back of this round
+        rounds += 1
+        if not changed:
+            break
+    nblk = _lib.load().hos_mesh_blocks(V)
+    _lib.check(min(nblk, 0), "hos_mesh_blocks")
+    ws = torch.empty(nblk, dtype=torch.int32, device=dev)
+    call("hos_mesh_component_ids", ptr(label, torch.int32), V, ptr(component, torch.int32), ptr(ws, torch.int32), ptr(words, torch.int32))
+    host = words.tolist()                                 # C and the invalid faces, one read-back
+    return label, component, int(host[3]), rounds, int(host[0])
+
+
+def mesh_component_measures(vertices, faces, component, count: int):
+    """Per component of a labelled mesh (`mesh_label`): (face_component int32 [F] -- the component of a face's first corner, -1 for a
+    face with a corner outside [0,V) --, n_vertices int64 [C], n_faces int64 [C], area float64 [C], volume float64 [C]); per face
+    area = |(b-a) x (c-a)| / 2 and volume = a . (b x c) / 6 on the fp32 `vertices` [V,3] promoted to double, summed per component in
+    a fixed order (a stable sort of the face ids by component, then hos_mesh_component_sums): two runs are bit-equal.  No read-back."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.HosLibraryError(f"mesh_component_measures: vertices must be [V,3], got {tuple(vertices.shape)}")
+    V, C = int(vertices.shape[0]), int(count)
+    _mesh_faces_check("mesh_component_measures", faces, V)
+    if component.dim() != 1 or component.shape[0] != V or component.dtype != torch.int32 or C < 0 or C > V:
+        raise _lib.HosLibraryError(f"mesh_component_measures: component must be int32 [{V}] and count in [0, {V}], got "
+                                   f"{component.dtype} {tuple(component.shape)} / {C}")
+    dev = vertices.device
+    F = int(faces.shape[0])
+    face_component = torch.full((F,), -1, dtype=torch.int32, device=dev)
+    n_vertices, n_faces = torch.zeros(C, dtype=torch.int64, device=dev), torch.zeros(C, dtype=torch.int64, device=dev)
+    area, volume = torch.zeros(C, dtype=torch.float64, device=dev), torch.zeros(C, dtype=torch.float64, device=dev)
+    if C == 0:
+        return face_component, n_vertices, n_faces, area, volume
+    _lib.require_gpu()
+    terms = torch.empty(F, 2, dtype=torch.float64, device=dev)
+    call("hos_mesh_component_terms", ptr(vertices) if F else 0, ptr(faces, torch.int32) if F else 0, ptr(component, torch.int32), V, F, C,
+         ptr(face_component, torch.int32) if F else 0, ptr(terms, torch.float64) if F else 0, ptr(n_vertices, torch.int64), ptr(n_faces, torch.int64))
+    if F > 0:
+        order = torch.sort(face_component, stable=True).indices.contiguous()             # the invalid faces (-1) come first
+        start = ((F - n_faces.sum()) + torch.cumsum(n_faces, 0) - n_faces).contiguous()
+        call("hos_mesh_component_sums", ptr(terms, torch.float64), ptr(order, torch.int64), ptr(start, torch.int64), ptr(n_faces, torch.int64),
+             F, C, ptr(area, torch.float64), ptr(volume, torch.float64))
+    return face_component, n_vertices, n_faces, area, volume
+
+
+def mesh_compact(keep, component, face_component, vertices, faces, colors=None, normals=None):
+    """The sub-mesh of the components with keep[c] != 0 (`keep` uint8 [C]) -> (vertices f32 [V',3], faces int32 [F',3], colors uint8
+    [V',3] or None, normals f32 [V',3] or None), vertices and faces in their original relative order, the faces renumbered by the
+    exclusive scan of keep[component[v]]; invalid faces (face_component -1) are never kept.  Count + scan, ONE read-back of (V', F'),
+    write (include/hosrender.h).  An empty mesh or an empty result returns empty tensors without the write launches."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.HosLibraryError(f"mesh_compact: vertices must be [V,3], got {tuple(vertices.shape)}")
+    V = int(vertices.shape[0])
+    _mesh_faces_check("mesh_compact", faces, V)
+    F = int(faces.shape[0])
+    if keep.dim() != 1 or keep.dtype != torch.uint8 or keep.shape[0] > V:
+        raise _lib.HosLibraryError(f"mesh_compact: keep must be uint8 [C] with C <= V = {V}, got {keep.dtype} {tuple(keep.shape)}")
+    C = int(keep.shape[0])
+    for name, t, n in (("component", component, V), ("face_component", face_component, F)):
+        if t.dim() != 1 or t.shape[0] != n or t.dtype != torch.int32:
+            raise _lib.HosLibraryError(f"mesh_compact: {name} must be int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    for name, t, dt in (("colors", colors, torch.uint8), ("normals", normals, torch.float32)):
+        if t is not None and (tuple(t.shape) != (V, 3) or t.dtype != dt):
+            raise _lib.HosLibraryError(f"mesh_compact: {name} must be {dt} {(V, 3)}, got {t.dtype} {tuple(t.shape)}")
+    dev = vertices.device
+    Vo = Fo = 0
+    if V > 0 and C > 0:
+        _lib.require_gpu()
+        lib = _lib.load()
+        nbv, nbf = lib.hos_mesh_blocks(V), lib.hos_mesh_blocks(F)
+        _lib.check(min(nbv, nbf, 0), "hos_mesh_blocks")
+        ws = torch.empty(nbv + nbf, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        call("hos_mesh_compact_count", ptr(keep, torch.uint8), C, ptr(component, torch.int32), V, ptr(faces, torch.int32) if F else 0,
+             ptr(face_component, torch.int32) if F else 0, F, ptr(ws, torch.int32), ptr(counts, torch.int32))
+        Vo, Fo = (int(c) for c in counts.tolist())        # the one host read-back of the compaction
+    out_v = torch.empty(Vo, 3, device=dev)
+    out_f = torch.empty(Fo, 3, dtype=torch.int32, device=dev)
+    out_c = None if colors is None else torch.empty(Vo, 3, dtype=torch.uint8, device=dev)
+    out_n = None if normals is None else torch.empty(Vo, 3, device=dev)
+    if Vo > 0:
+        new_id = torch.empty(V, dtype=torch.int32, device=dev)
+        call("hos_mesh_compact_write", ptr(keep, torch.uint8), C, ptr(component, torch.int32), V, ptr(faces, torch.int32) if F else 0,
+             ptr(face_component, torch.int32) if F else 0, F, ptr(ws, torch.int32), ptr(new_id, torch.int32), ptr(vertices),
+             ptr(colors, torch.uint8), ptr(normals), Vo, Fo, ptr(out_v), ptr(out_c, torch.uint8), ptr(out_n), ptr(out_f, torch.int32) if Fo else 0)
+    return out_v, out_f, out_c, out_n

@@ -1037,6 +1037,72 @@ int hos_warp_invert(const float* target, const float* guess, const float* R_b, c
                     const float* bbox_min, const float* bbox_scale, int iters, float tol, float max_step, int64_t P, float* p_out,
                     float* x_skel, float* mask, float* residual, int32_t* status, float* jac, hos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh components (this build's addition; the reference has no counterpart): the connected pieces of a triangle mesh -- two vertices
+ * are connected when a face names both -- labelled, counted, measured, and the sub-mesh of the pieces the caller keeps.  faces int32
+ * [F,3] over V vertices.  A face with a corner outside [0,V) is ignored by every kernel and counted (hos_raster_faces' rule for such
+ * triangles); a face (a,a,b) is valid and connects a and b; a vertex no face names is a component of its own.  Every entry: negative
+ * sizes and null pointers HOS_E_ARG, V or F >= 2^31 - 256 (ids, block counts and scanned totals are int32) or C > V HOS_E_SHAPE, all
+ * before any launch; V = 0 launches nothing.  hos_mesh_blocks(n) = ceil(n / 256), the blocks of n vertices or faces (host
+ * arithmetic; a negative code for a bad n).
+ * ------------------------------------------------------------------------------------------ */
+int hos_mesh_blocks(int64_t n);
+
+/* label int32 [V]: label[v] = the smallest vertex id of v's component.  That definition fixes the result whatever the scheduling.
+ *   hos_mesh_label_begin   label[v] = v; words int32 [4] = 0: [0] `invalid` (faces with a corner outside [0,V)), [1] / [2] `changed` of
+ *                          the even / odd rounds, [3] the component count hos_mesh_component_ids writes.
+ *   hos_mesh_label_round   round number `round` = 0, 1, ...: two launches.  Hook, one thread per face: m = the minimum of the three
+ *                          labels read; for each corner x with label read l_x > m, atomicMin(&label[x], m) and atomicMin(&label[l_x], m).
+ *                          Jump, one thread per vertex: label[v] := label[label[v]], twice, written with atomicMin.  A thread whose
+ *                          atomicMin returned more than it wrote sets words[1 + (round & 1)]; the hook of round k zeroes the word of
+ *                          round k + 1 (no thread of round k touches it) and, in round 0, counts the invalid faces.  F = 0 launches
+ *                          nothing.
+ * The host repeats rounds until one leaves its word at 0: then every face's labels are equal and every label is a root, which is the
+ * definition above.  Labels are only ever lowered, and only by device-scope integer atomicMin; a plain load of a label may be stale
+ * inside a launch, which costs rounds, never the result; no kernel waits for, polls or hands data to another workgroup, no loop's
+ * trip count depends on another thread, the launch boundary is the only synchronisation.  Min-propagation over faces alone reaches
+ * the fixed point within diameter + 2 <= V + 2 rounds: the host refuses to go on past V + 2. */
+int hos_mesh_label_begin(int64_t V, int32_t* label, int32_t* words, hos_stream_t stream);
+int hos_mesh_label_round(const int32_t* faces, int64_t F, int64_t V, int round, int32_t* label, int32_t* words, hos_stream_t stream);
+
+/* component int32 [V] = the rank of label[v] among the roots (label[r] == r) in ascending order; words[3] = C, the number of roots.
+ * Four launches: roots per 256-vertex block, one scan workgroup, the roots' ranks, then every other vertex reads its root's.
+ * ws int32 [hos_mesh_blocks(V)].  label must be a converged labelling (a label that is no vertex id gives component -1). */
+int hos_mesh_component_ids(const int32_t* label, int64_t V, int32_t* component, int32_t* ws, int32_t* words, hos_stream_t stream);
+
+/* Per-component measures, in two steps around a stable sort of the face ids by face_component (the caller's; any stable sort).
+ *   hos_mesh_component_terms  face_component int32 [F] = component of the face's first corner, -1 for an invalid face; terms double
+ *                             [F,2] = (|(b - a) x (c - a)| / 2, a . (b x c) / 6) of the fp32 vertices promoted to double, every
+ *                             product and sum rounded on its own: ux = bx - ax ...; n = (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx);
+ *                             area = sqrt((nx nx + ny ny) + nz nz) / 2; m = b x c likewise; volume = ((ax mx + ay my) + az mz) / 6;
+ *                             (0, 0) for an invalid face.  n_vertices / n_faces int64 [C], ZEROED BY THE CALLER, += the vertices /
+ *                             valid faces of each component (integer atomics: exact).  vertices f32 [V,3].  C = 0 launches nothing,
+ *                             F = 0 counts the vertices alone.
+ *   hos_mesh_component_sums   area / volume double [C] = the sums of the terms of the faces order[start[c] .. start[c] + n_faces[c]),
+ *                             order int64 [F] the sorted face ids, start int64 [C].  One workgroup per component: thread t adds the
+ *                             faces t, t + 256, ... of the range in that order, then a fixed tree over the 256 partial sums -- no
+ *                             floating-point atomics, two runs are bit-equal.  A range or an id outside [0,F) contributes nothing. */
+int hos_mesh_component_terms(const float* vertices, const int32_t* faces, const int32_t* component, int64_t V, int64_t F, int C,
+                             int32_t* face_component, double* terms, int64_t* n_vertices, int64_t* n_faces, hos_stream_t stream);
+int hos_mesh_component_sums(const double* terms, const int64_t* order, const int64_t* start, const int64_t* n_faces, int64_t F, int C,
+                            double* area, double* volume, hos_stream_t stream);
+
+/* The sub-mesh of the components with keep[c] != 0 (uint8 [C]) in the original relative order: new vertex id = the exclusive scan of
+ * keep[component[v]] in vertex order; a face is kept iff face_component[f] >= 0 is kept (and so is every corner, which follows for a
+ * labelled mesh), the kept faces stay in face order, renumbered.  Invalid faces are never kept.
+ *   hos_mesh_compact_count  two launches: kept vertices / faces per 256-block into ws int32 [hos_mesh_blocks(V) + hos_mesh_blocks(F)],
+ *                           one scan workgroup; counts int32 [2] = (V', F'), read back by the host.
+ *   hos_mesh_compact_write  two launches: out_vertices f32 [V',3] (and out_colors uint8 [V',3] of colors, out_normals f32 [V',3] of
+ *                           normals; each pair both NULL or neither) plus new_id int32 [V] (-1 for a dropped vertex), then out_faces
+ *                           int32 [F',3].  Vout = V' and Fout = F' bound every store.  V' = 0 launches nothing.
+ * F = 0 compacts the vertices alone. */
+int hos_mesh_compact_count(const unsigned char* keep, int C, const int32_t* component, int64_t V, const int32_t* faces,
+                           const int32_t* face_component, int64_t F, int32_t* ws, int32_t* counts, hos_stream_t stream);
+int hos_mesh_compact_write(const unsigned char* keep, int C, const int32_t* component, int64_t V, const int32_t* faces,
+                           const int32_t* face_component, int64_t F, const int32_t* ws, int32_t* new_id, const float* vertices,
+                           const unsigned char* colors, const float* normals, int64_t Vout, int64_t Fout, float* out_vertices,
+                           unsigned char* out_colors, float* out_normals, int32_t* out_faces, hos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

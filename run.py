@@ -31,6 +31,11 @@ inverted backward warp -- one topology per state -- <logdir>/mesh_track/template
 `run.run_mesh_bkgd` (stages 1 and 3, with `--scene_dir`; this build's addition) writes the BACKGROUND scene of every object state as
 a triangle mesh in the same scaled-world coordinates, <logdir>/mesh_bkgd/time_<t>.ply + meshes.json (`mesh.extract_bkgd`;
 `run.mesh_bkgd_box` (-1,-1,-1, 1,1,1), the same `run.mesh_resolution` / `run.mesh_level`).
+`run.mesh_min_component = r` (0 <= r <= 1, default 0.0 = off; this build's addition) drops the floaters of every mesh the four mesh
+outputs write: the connected components whose area is below r times the largest component's (`mesh.drop_floaters`,
+hos_components.hip) -- the canonical and background meshes, each frame mesh (its preview and fit included) and the templates of
+`run.run_mesh_track`, filtered once per state before any frame is tracked.  The rows of meshes.json then describe the written mesh
+and gain `components` (count, kept, what was dropped).  At 0 every file is byte-identical to a run without the binding.
 The reference's .gin files parse unchanged (hosnerf_amd/gin_lite.py).
 
 What is NOT here: Lightning's Trainer (a plain loop drives `training_step` / `optimizer_step` / checkpoints the way the Trainer
@@ -166,6 +171,7 @@ def run(args, gin):
         if model_name == "state_humanobject":
             raise SystemExit("run.run_mesh_bkgd extracts the background scene (stage 1 `state_mipnerf360`, stage 3 `hosnerf`); stage 2 has no background model")
         mesh_bkgd_box(kw)                             # an empty or non-finite box stops the run before anything is trained
+    mesh_min_component(kw)                            # so does a ratio outside [0, 1]
     dataset_name = kw.get("dataset_name", "synthetic")
     scene = args.scene_name or "scene"
     exp_name = f"{model_name}_{dataset_name}_{scene}_{str(args.seed).zfill(3)}"          # S3/run.py:108-110
@@ -588,17 +594,18 @@ def extract_meshes(kw, lit, scene, ckpt, logdir, dev, rank, world):
     mesh, from `last.ckpt`, at the times of `tpose.tpose_times` -- `mesh.extract` at `run.mesh_resolution` (256) and `run.mesh_level`
     (0.5) -> <logdir>/mesh/time_{:06}.ply (binary PLY, per-vertex albedo) and <logdir>/mesh/meshes.json (per time: state, V, F,
     volume, area, level, spacing, dims).  With several ranks the states are dealt round-robin, each rank writes its own .ply and
-    rank 0 the JSON.  `results.json` is not touched."""
+    rank 0 the JSON.  `results.json` is not touched.  `run.mesh_min_component` > 0: the floaters are dropped (`mesh_min_component`)."""
     from hosnerf_amd import mesh, tpose
     load_last(lit, scene, ckpt, "run.run_mesh", "canonical joints and box")
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
+    floaters = floater_kwargs(kw)
     net = lit.human
     turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
     times = tpose.tpose_times(net.transitions_times)
 
     def job(j):
-        m = mesh.extract(net, turn, times[j], resolution=resolution, level=level)
-        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level)}
+        m = mesh.extract(net, turn, times[j], resolution=resolution, level=level, **floaters)
+        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level), **components_row(m, floaters)}
 
     write_mesh_set(os.path.join(logdir, "mesh"), len(times), rank, world, job, lambda r: "time_{:06}".format(r["time"]))
     if rank == 0:
@@ -626,9 +633,12 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     (`freeview.save_mesh_maps`); the human-object alone is rendered from the same camera (`eval.render_human_frame` of
     `scene.human_frame`, maps and median depth), and the frame's row gets `fit`: `render` (`mesh.fit` against the render's alpha /
     depth_median) and `mask` (against the scene's subject mask, silhouette only).  `run.mesh_level_sweep = (l0, l1, ...)` adds
-    `sweep`: `mesh.level_sweep` of the same field against the render, one row per level."""
+    `sweep`: `mesh.level_sweep` of the same field against the render, one row per level.  `run.mesh_min_component` > 0: the
+    floaters are dropped (`mesh_min_component`) before the normals and `mesh.to_space`; the preview and the fit are of the
+    filtered body mesh, the sweep's re-marches stay unfiltered."""
     from hosnerf_amd import mesh
     load_last(lit, scene, ckpt, "run.run_mesh_frames", "the frames' poses, boxes and cameras")
+    floaters = floater_kwargs(kw)
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
     preview, sweep = bool(kw.get("mesh_preview", False)), mesh_level_sweep(kw)
@@ -639,11 +649,11 @@ def extract_frame_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     def job(j):
         try:
             m = mesh.extract_frame(net, scene.frame_pose(idxs[j]), resolution=resolution, level=level, space=space, normals=normals,
-                                   **({"keep_body": True} if preview else {}))          # without the switch: the call as it always was
+                                   **({"keep_body": True} if preview else {}), **floaters)      # without the switches: the call as it always was
         except ValueError as e:                      # cameras without smpl_to_scale_world: say so and stop, no half-written sequence
             raise SystemExit(f"run.run_mesh_frames: {e}")
         row = {"frame_name": m["frame_name"], "time": m["time"], **mesh_measures(m, level), "space": space,
-               "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+               "to_world": [[float(x) for x in r] for r in m["to_world"]], **components_row(m, floaters)}
         if preview:
             row.update(preview_frame_mesh(lit, scene, idxs[j], m, folder, sweep))
         return m["frame_name"], m, row
@@ -672,12 +682,14 @@ def track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
     residual {median, p99, max}, mask_ratio {median, min, max} of mask / mask_canonical over the vertices whose canonical mask exceeds 1e-4,
     volume, area, level, spacing, dims, space, to_world).  The templates are extracted once per state on every rank that needs them;
     the frames are dealt round-robin, each rank writes its own files and rank 0 the JSON (and the templates).  `results.json` is not
-    touched."""
+    touched.  `run.mesh_min_component` > 0: every template loses its floaters (`mesh_min_component`) once, when it is extracted and
+    before any frame is tracked; template_state_<s>.ply is the filtered template and every row gains its `components`."""
     import numpy as np
     from hosnerf_amd import formats, mesh, tpose
     load_last(lit, scene, ckpt, "run.run_mesh_track", "the frames' poses and the canonical joints and box")
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     space, normals = str(kw.get("mesh_space", "world")), bool(kw.get("mesh_normals", True))
+    floaters = floater_kwargs(kw)
     net = lit.human
     turn = tpose.TposeTurn(scene.canonical_joints, scene.canonical_bbox, int(lit.cfg.mweight_volume.volume_size), dev)
     state_time = {mesh.select_state(float(t), net.transitions_times): float(t) for t in tpose.tpose_times(net.transitions_times)}
@@ -688,7 +700,7 @@ def track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
 
     def template_of(state):
         if state not in templates:
-            templates[state] = mesh.extract(net, turn, state_time[state], resolution=resolution, level=level, normals=normals)
+            templates[state] = mesh.extract(net, turn, state_time[state], resolution=resolution, level=level, normals=normals, **floaters)
         return templates[state]
 
     def job(j):
@@ -707,7 +719,7 @@ def track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
                "mask_ratio": {"median": float(ratio.median()), "min": float(ratio.min()), "max": float(ratio.max())} if ratio.numel()
                else {"median": 0.0, "min": 0.0, "max": 0.0},
                "volume": m["volume"], "area": m["area"], "level": level, "spacing": m["spacing"], "dims": list(m["dims"]), "space": space,
-               "to_world": [[float(x) for x in r] for r in m["to_world"]]}
+               "to_world": [[float(x) for x in r] for r in m["to_world"]], **components_row(tpl, floaters)}
         return m["frame_name"], m, row
 
     rows = write_mesh_set(folder, len(idxs), rank, world, job, lambda r: r["frame_name"])
@@ -723,7 +735,8 @@ def track_meshes(args, kw, lit, scene, ckpt, logdir, dev, rank, world):
 
 def mesh_level_sweep(kw):
     """`run.mesh_level_sweep` = (l0, l1, ...): the levels `run.mesh_preview` re-marches each frame's field at, a tuple of finite
-    floats; absent or empty = no sweep -> tuple."""
+    floats; absent or empty = no sweep -> tuple.  The sweep scores UNFILTERED re-marches: `run.mesh_min_component` does not apply to
+    them (a level is judged by everything it extracts, floaters included)."""
     levels = kw.get("mesh_level_sweep", ())
     ok = isinstance(levels, (tuple, list)) and all(isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x) for x in levels)
     if not ok:
@@ -752,6 +765,26 @@ def preview_frame_mesh(lit, scene, idx: int, m, folder: str, sweep=()):
     return out
 
 
+def mesh_min_component(kw):
+    """`run.mesh_min_component` = r: every written mesh keeps the connected components whose area is at least r times the largest
+    component's (`mesh.drop_floaters(min_area_ratio=r)`).  A number in [0, 1], default 0.0 = no filtering, or the run stops."""
+    r = kw.get("mesh_min_component", 0.0)
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0.0 <= float(r) <= 1.0:
+        raise SystemExit(f"run.mesh_min_component = {r!r}: a number in [0, 1], the smallest component kept as a share of the largest one's area (0 = keep all)")
+    return float(r)
+
+
+def floater_kwargs(kw):
+    """What the extractors are handed for `run.mesh_min_component`: nothing at 0 -- the call as it always was."""
+    r = mesh_min_component(kw)
+    return {"min_area_ratio": r} if r > 0.0 else {}
+
+
+def components_row(m, floaters):
+    """The `components` entry a row of meshes.json gains with `run.mesh_min_component` > 0; nothing without."""
+    return {"components": m["components"]} if floaters else {}
+
+
 def mesh_bkgd_box(kw):
     """`run.mesh_bkgd_box` = (xmin, ymin, zmin, xmax, ymax, zmax), default the cube (-1,-1,-1, 1,1,1) about the region the scene
     contraction leaves linear; a larger box is legal (the contraction takes any point).  Six finite numbers with min < max on every
@@ -774,17 +807,19 @@ def extract_bkgd_meshes(kw, lit, model_name, source, ckpt, logdir, dev, rank, wo
     in the background rays' own space, the scene's scaled world: the space the stage-3 z-merge maps the human samples into by
     `newsmpl_to_scale_world` (hosnerf.py, `ops.merge_composite`) and therefore the one `run.mesh_space = "world"` writes the frame
     meshes in -- mesh_frames/*.ply and mesh_bkgd/*.ply load aligned.  With several ranks the states are dealt round-robin, each rank
-    writes its own .ply and rank 0 the JSON.  `results.json` is not touched."""
+    writes its own .ply and rank 0 the JSON.  `results.json` is not touched.  `run.mesh_min_component` > 0: the floaters are dropped
+    (`mesh_min_component`) before the colour query, which then runs on the kept vertices only."""
     from hosnerf_amd import mesh, tpose
     load_last(lit, source, ckpt, "run.run_mesh_bkgd", "the scene whose checkpoint is meshed")
+    floaters = floater_kwargs(kw)
     resolution, level = int(kw.get("mesh_resolution", 256)), float(kw.get("mesh_level", 0.5))
     box = mesh_bkgd_box(kw)
     model = lit.model if model_name == "state_mipnerf360" else lit.net.model
     times = tpose.tpose_times(model.mlps[-1].transitions_times)
 
     def job(j):
-        m = mesh.extract_bkgd(model, box, times[j], resolution=resolution, level=level)
-        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level), "box": m["box"]}
+        m = mesh.extract_bkgd(model, box, times[j], resolution=resolution, level=level, **floaters)
+        return "time_{:06}".format(times[j]), m, {"time": times[j], **mesh_measures(m, level), "box": m["box"], **components_row(m, floaters)}
 
     write_mesh_set(os.path.join(logdir, "mesh_bkgd"), len(times), rank, world, job, lambda r: "time_{:06}".format(r["time"]))
     if rank == 0:
